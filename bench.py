@@ -15,12 +15,21 @@ clips.  Workload presets (--config): 2 = BASELINE.json configs[1] (arch_mdm_l, 6
 Clips are independent, so ranks shard them with no data-path collective (weak scaling); the only exchange is the RCCL
 all_gather of the sampled poses at the end of every loop, which is inside the timed region.
 
-value = (clips of all ranks) * T * K / (max-over-ranks wall time of the K timed loops), inputs resident in HBM.
-The line also carries, measured in the same run: `check` (max abs error of one denoiser evaluation against the oracle
-for every dtype reported), `roofline` (dominant kernel of the headline dtype, HIP events on the launch stream; `peak` is the
-nominal figure, `mfma_sustained` what register-only MFMA loops reach on this very board under its power management),
-`other_dtypes` (the same workload in the other arithmetic modes, among them the reference's own fp32) and
-`cpu_baseline` (the oracle on the host cores).
+value = (clips of all ranks) * T * K / (max-over-ranks wall time of the K timed loops), inputs resident in HBM;
+ms_per_step = that wall time / K.  A plain run sets up, warms up, times the K steps and prints the line (with `finite` and,
+in f16x3, the range flag of the timed loops); nothing else is measured.
+
+--full adds, measured in the same run after the timed steps: `check` (max abs error of one denoiser evaluation against the
+oracle for every dtype reported), `roofline` (dominant kernel of the headline dtype, HIP events on the launch stream; `peak` is
+the nominal figure, `mfma_sustained` what register-only MFMA loops reach on this very board under its power management),
+`power` (package power / clock during the timed loops), `other_dtypes` (the same workload in the other arithmetic modes, among
+them the reference's own fp32), `torch_rocm_baseline` (the same workload through PyTorch-ROCm's libraries) and `cpu_baseline`
+(the oracle on the host cores).
+
+--dump-outputs DIR writes what the timed path returned in its last timed step, as float32 .npy files (rank 0; all ranks'
+clips when N > 1): DIR/sample.npy, the (clips, 99, 1, T) sampled poses (--config 4: DIR/refine_pose_repr.npy, (B, T, 99)).
+Weights, conditioning and noise seeds are fixed, so the same arguments give the same inputs on every run.  Above 64 MB in
+all, a fixed seeded subset of the clips is written instead (sorted clip order).
 """
 from __future__ import annotations
 
@@ -226,6 +235,26 @@ def checks_ok(finite_by, range_flags, check):
     and every in-run oracle comparison is inside its per-dtype tolerance (NaN fails).  bench.py exits 3 when this is False."""
     ok = all(finite_by.values()) and not any(range_flags.values())
     return ok and all(e == e and e < CHECK_TOL[d] for d, e in check.items())
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """--dump-outputs: each array (clips first) as dirname/<name>.npy in float32.  When they exceed max_bytes together, the same
+    fixed seeded subset of clips (sorted) is written of every array."""
+    import numpy as np
+
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > max_bytes:
+        n = min(a.shape[0] for a in arrays.values())
+        keep = max(1, int(n * max_bytes // total))
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[idx]) for k, a in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
 
 
 def usable_cores() -> int:
@@ -486,14 +515,22 @@ def parse_args(argv):
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: CPU test of the launch/gather path (needs --sampler)")
     ap.add_argument("--sampler", default=None, help="test hook (only with --backend gloo): module:callable replacing the HIP sampler (tests/bench_stub.py)")
     ap.add_argument("--fp32-loops", type=int, default=3, help="timed loops of the strict-fp32 entry of the line (N = 1 only; 0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the oracle check, roofline, power, other dtypes and the library / CPU baselines "
+                         "(the options above that shape them act only with --full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     args = ap.parse_args(argv)
     if args.sampler and args.backend != "gloo":
         ap.error("--sampler is the CPU test hook of the launch / gather path: it needs --backend gloo")
+    if args.profile_out and not args.full:
+        ap.error("--profile-out is part of the roofline measurement: it needs --full")
     preset = CONFIGS[args.config]
     if args.steps is None:
         args.steps = 200 if args.config == 4 else 3
     if args.warmup is None:
         args.warmup = 20 if args.config == 4 else 1
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config == 4:
         args.arch = "arch_refine"
     elif args.arch == "arch_refine":
@@ -527,9 +564,9 @@ def main_refine(args, dev, ptrace):
     x_in = torch.randn(B, T, 99, generator=g).to(dev)
     h2o = (torch.randn(B, T, 778, generator=g).abs() * 0.05).to(dev)
     cond_dev = {k: (v.to(dev) if hasattr(v, "to") else v) for k, v in cond.items()}
-    n_check = max(0, min(args.check_clips, B))
+    n_check = max(0, min(args.check_clips, B)) if args.full else 0
     ref = None
-    if n_check or not args.no_cpu_baseline:  # the checker / CPU baseline: the only use of oracle/ here
+    if n_check or (args.full and not args.no_cpu_baseline):  # the checker / CPU baseline: the only use of oracle/ here
         from oracle import mdm_oracle as O
 
         oarch = O.ARCH_REFINE
@@ -538,7 +575,7 @@ def main_refine(args, dev, ptrace):
         with torch.no_grad():
             ref = O.refine_forward(sd, oarch, x_in[:n_check].cpu(), h2o[:n_check].cpu(), sub)
 
-    def run_mode(dt, steps, warmup):
+    def run_mode(dt, steps, warmup, profile=True):
         ctx = TamfContext(arch, B, T, precision=dt, device=dev, kind="R")
         ctx.load_state_dict(sd)
 
@@ -557,6 +594,11 @@ def main_refine(args, dev, ptrace):
         w1 = time.time()
         flag = bool(ctx.status_flags(clear=True) & 1) if dt == "f16x3" else False
         err = float((out[:n_check].cpu() - ref).abs().max()) if ref is not None else None
+        finite = bool(torch.isfinite(out).all().item())
+        res = {"elapsed": el, "wall": (w0, w1), "err": err, "flag": flag, "finite": finite, "out": out.cpu()}
+        if not profile:
+            ctx.close()
+            return res
         agg, reps = {}, 5
         for r in range(reps + 1):
             rows = ctx.refine_profile(x_in, h2o)
@@ -568,43 +610,21 @@ def main_refine(args, dev, ptrace):
         prof = [{"kernel": n, "launches_per_forward": a[2] // reps, "avg_ms": a[0] / a[2], "algorithmic_gflop_per_launch": a[1] / a[2] / 1e9,
                  "tflops": (a[1] / a[2]) / (a[0] / a[2] * 1e-3) / 1e12 if a[0] > 0 else 0.0, "share": a[0] / sum(x[0] for x in agg.values())}
                 for n, a in sorted(agg.items(), key=lambda kv: -kv[1][0])]
-        finite = bool(torch.isfinite(out).all().item())
         ctx.close()
-        return {"elapsed": el, "wall": (w0, w1), "err": err, "flag": flag, "finite": finite, "profile": prof, "forward_gflop": fwd_flops / 1e9}
+        res.update({"profile": prof, "forward_gflop": fwd_flops / 1e9})
+        return res
 
-    head = run_mode(args.dtype, args.steps, args.warmup)
+    head = run_mode(args.dtype, args.steps, args.warmup, profile=args.full)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"refine_pose_repr": head["out"].numpy()})
+    ms_batch = head["elapsed"] / args.steps * 1e3
     power = None
     if ptrace is not None:
         pr = torch.cuda.get_device_properties(dev)
         pci = "%04x:%02x:%02x.0" % (pr.pci_domain_id, pr.pci_bus_id, pr.pci_device_id) if hasattr(pr, "pci_bus_id") else None
         power = ptrace.finish(head["wall"][0], head["wall"][1], pci)
-    peak = PEAK_TFLOPS[args.dtype]
-    dom = head["profile"][0]
-    ms_batch = head["elapsed"] / args.steps * 1e3
-    whole_tf = head["forward_gflop"] * 1e9 / (ms_batch * 1e-3) / 1e12
-    roofline = {"bound": "mfma", "kernel": dom["kernel"], "dtype": args.dtype, "mfma_per_product": MFMA_PER_PRODUCT[args.dtype],
-                "achieved": dom["tflops"], "peak": peak, "unit": "TFLOP/s", "frac": dom["tflops"] / peak, "traffic": None,
-                "avg_launch_ms": dom["avg_ms"], "share_of_step": dom["share"], "forward_algorithmic_gflop": head["forward_gflop"],
-                "launches_per_forward": sum(r["launches_per_forward"] for r in head["profile"]),
-                "kernels": [{k: (round(v, 5) if isinstance(v, float) else v) for k, v in r.items()} for r in head["profile"]],
-                "note": "a 1.2-ms forward of 50 launches over 12 736 token rows of width 256: launch ramps and epilogues, not a roofline, bound it (SURVEY.md 8d)"}
     check = {args.dtype: head["err"]} if head["err"] is not None else {}
     finite_by, range_flags = {args.dtype: head["finite"]}, ({args.dtype: head["flag"]} if args.dtype == "f16x3" else {})
-    other = {}
-    for dt in [d for d in args.also.split(",") if d and d != args.dtype]:
-        r = run_mode(dt, max(20, args.steps // 4), 5)
-        ms = r["elapsed"] / max(20, args.steps // 4) * 1e3
-        other[dt] = {"value": B * T / ms * 1e3, "unit": "frames/s", "ms_per_batch": ms, "finite": r["finite"],
-                     "whole_path_tflops": r["forward_gflop"] / ms, "whole_path_frac_of_peak": r["forward_gflop"] / ms / PEAK_TFLOPS[dt],  # (GFLOP per ms = TFLOP/s)
-                     "dominant_kernel": r["profile"][0]["kernel"], "dominant_kernel_frac": r["profile"][0]["tflops"] / PEAK_TFLOPS[dt]}
-        finite_by[dt] = r["finite"]
-        if r["err"] is not None:
-            check[dt] = r["err"]
-        if dt == "f16x3":
-            range_flags[dt] = r["flag"]
-    if "f32" in other:
-        roofline["f32_value"], roofline["f32_ms_per_batch"] = other["f32"]["value"], other["f32"]["ms_per_batch"]
-        roofline["f32_whole_path_frac"] = other["f32"]["whole_path_frac_of_peak"]
     line = {
         "metric": "refined motion frames/s (arch_refine trunk, one forward per batch)", "value": B * T * args.steps / head["elapsed"],
         "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_batch, "higher_is_better": True,
@@ -612,9 +632,34 @@ def main_refine(args, dev, ptrace):
         "data": "synthetic (random-init weights of arch_refine, N(0,1) G samples, |N(0, 5 cm)| hand->object distances, N(0,1) conditioning)",
         "config": {"workload": f"arch_refine trunk B={B} T={T}, one forward per step ({CONFIGS[4]['label']})", "preset": 4, "clips_per_gpu": B,
                    "frames": T, "parallelism": "single GPU"},
-        "ms_per_batch": ms_batch, "whole_path_tflops": whole_tf, "whole_path_frac_of_peak": whole_tf / peak, "finite": head["finite"],
-        "roofline": roofline, "kernels": head["profile"][:8],
+        "ms_per_batch": ms_batch, "finite": head["finite"],
     }
+    other = {}
+    if args.full:
+        peak = PEAK_TFLOPS[args.dtype]
+        dom = head["profile"][0]
+        whole_tf = head["forward_gflop"] * 1e9 / (ms_batch * 1e-3) / 1e12
+        roofline = {"bound": "mfma", "kernel": dom["kernel"], "dtype": args.dtype, "mfma_per_product": MFMA_PER_PRODUCT[args.dtype],
+                    "achieved": dom["tflops"], "peak": peak, "unit": "TFLOP/s", "frac": dom["tflops"] / peak, "traffic": None,
+                    "avg_launch_ms": dom["avg_ms"], "share_of_step": dom["share"], "forward_algorithmic_gflop": head["forward_gflop"],
+                    "launches_per_forward": sum(r["launches_per_forward"] for r in head["profile"]),
+                    "kernels": [{k: (round(v, 5) if isinstance(v, float) else v) for k, v in r.items()} for r in head["profile"]],
+                    "note": "a 1.2-ms forward of 50 launches over 12 736 token rows of width 256: launch ramps and epilogues, not a roofline, bound it (SURVEY.md 8d)"}
+        for dt in [d for d in args.also.split(",") if d and d != args.dtype]:
+            r = run_mode(dt, max(20, args.steps // 4), 5)
+            ms = r["elapsed"] / max(20, args.steps // 4) * 1e3
+            other[dt] = {"value": B * T / ms * 1e3, "unit": "frames/s", "ms_per_batch": ms, "finite": r["finite"],
+                         "whole_path_tflops": r["forward_gflop"] / ms, "whole_path_frac_of_peak": r["forward_gflop"] / ms / PEAK_TFLOPS[dt],  # (GFLOP per ms = TFLOP/s)
+                         "dominant_kernel": r["profile"][0]["kernel"], "dominant_kernel_frac": r["profile"][0]["tflops"] / PEAK_TFLOPS[dt]}
+            finite_by[dt] = r["finite"]
+            if r["err"] is not None:
+                check[dt] = r["err"]
+            if dt == "f16x3":
+                range_flags[dt] = r["flag"]
+        if "f32" in other:
+            roofline["f32_value"], roofline["f32_ms_per_batch"] = other["f32"]["value"], other["f32"]["ms_per_batch"]
+            roofline["f32_whole_path_frac"] = other["f32"]["whole_path_frac_of_peak"]
+        line.update({"whole_path_tflops": whole_tf, "whole_path_frac_of_peak": whole_tf / peak, "roofline": roofline, "kernels": head["profile"][:8]})
     if power is not None:
         line["power"] = power
     if check:
@@ -626,7 +671,7 @@ def main_refine(args, dev, ptrace):
     line["check_ok"] = checks_ok(finite_by, range_flags, check)
     if other:
         line["other_dtypes"] = other
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cores = usable_cores()
         torch.set_num_threads(cores)
         times = []
@@ -665,7 +710,7 @@ def main(argv=None, sampler_factory=None):
     import torch.distributed as dist
 
     # ... nor from a process that has ALREADY initialised the GPU (bench.main called from a test or a notebook that used the GPU before)
-    if int(os.environ.get("RANK", "0")) == 0 and not args.sampler and not args.no_power and not under_profiler and not torch.cuda.is_initialized():
+    if args.full and int(os.environ.get("RANK", "0")) == 0 and not args.sampler and not args.no_power and not under_profiler and not torch.cuda.is_initialized():
         ptrace = PowerTrace()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -746,6 +791,8 @@ def main(argv=None, sampler_factory=None):
         res = one_loop(k)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # (before --full reuses `out` for the other dtypes)
+        dump_outputs(args.dump_outputs, {"sample": res.cpu().numpy()})
     power = None
     if ptrace is not None:
         pci = None
@@ -798,7 +845,7 @@ def main(argv=None, sampler_factory=None):
     # in-run parity: one denoiser evaluation of the first clips of this batch against the oracle, per dtype reported
     check = {}
     check_in = None
-    if rank == 0 and args.check_clips > 0 and not stub:
+    if args.full and rank == 0 and args.check_clips > 0 and not stub:
         nc = min(args.check_clips, B)
         g = torch.Generator().manual_seed(4242)
         xc = torch.randn(B, 99, 1, T, generator=g)
@@ -874,7 +921,7 @@ def main(argv=None, sampler_factory=None):
         }
 
     roofline = None
-    if rank == 0 and not stub:
+    if args.full and rank == 0 and not stub:
         sampler.set_cond(cond_dev)
         roofline = roofline_of(sampler, args.dtype, args.profile_out)
 
@@ -883,7 +930,7 @@ def main(argv=None, sampler_factory=None):
     # reported gets its own finiteness test, oracle check and dominant-kernel roofline
     other = {}
     finite_by = {args.dtype: finite}
-    if rank == 0 and world == 1 and not stub:
+    if args.full and rank == 0 and world == 1 and not stub:
         extra = [d for d in args.also.split(",") if d and d != args.dtype]
         if args.fp32_loops > 0 and args.dtype != "f32" and "f32" not in extra:
             extra.append("f32")
@@ -1009,7 +1056,7 @@ def main(argv=None, sampler_factory=None):
         line["check_ok"] = ok  # every reported dtype: finite samples, oracle check inside its tolerance, no range flag
         if other:
             line["other_dtypes"] = other
-        if not args.no_torch_baseline and world == 1 and not stub:
+        if args.full and not args.no_torch_baseline and world == 1 and not stub:
             # same-box library yardstick: the reference's own op sequence through PyTorch-ROCm (hipBLASLt / SDPA), after every timed region
             try:
                 tb = torch_rocm_baseline(args.arch, sd, cond, B, T, N, dev, check_in)
@@ -1022,7 +1069,7 @@ def main(argv=None, sampler_factory=None):
                 "headline_%s_over_library_f32" % args.dtype: value / tb["best_f32"]["value"] if "best_f32" in tb else None,
                 "f32_over_library_f32": mine["f32"] / tb["best_f32"]["value"] if mine.get("f32") and "best_f32" in tb else None,
                 "bf16_over_library_bf16": mine["bf16"] / tb["best_bf16"]["value"] if mine.get("bf16") and "best_bf16" in tb else None}
-        if not args.no_cpu_baseline and world == 1 and not stub:  # at N = 1 only (one host measurement, not one per scaling point)
+        if args.full and not args.no_cpu_baseline and world == 1 and not stub:  # at N = 1 only (one host measurement, not one per scaling point)
             line["cpu_baseline"] = cpu_baseline(args.arch, sd, B, T, N)
             line["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
         print(json.dumps(line), flush=True)

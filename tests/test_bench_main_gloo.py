@@ -87,6 +87,7 @@ def test_bench_presets():
     assert a.batch == 64 and a.dtype == "bf16"
     a = bench.parse_args([])
     assert a.batch == 64 and a.frames == 196 and a.ddpm_steps == 1000 and a.gpus == 1 and a.steps == 3 and a.warmup == 1
+    assert a.full is False and a.dump_outputs is None  # a plain run measures the headline only
     a = bench.parse_args(["--config", "4"])  # BASELINE configs[3]: the R trunk, one forward per step
     assert a.arch == "arch_refine" and a.batch == 64 and a.frames == 196 and a.steps == 200 and a.warmup == 20
     a = bench.parse_args(["--config", "4", "--steps", "7", "--warmup", "2"])
@@ -95,6 +96,11 @@ def test_bench_presets():
 
     with pytest.raises(SystemExit):
         bench.parse_args(["--arch", "arch_refine"])
+    with pytest.raises(SystemExit):  # the per-kernel profile is part of --full's roofline
+        bench.parse_args(["--profile-out", "p.json"])
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    assert bench.parse_args(["--full", "--profile-out", "p.json"]).full
     assert bench.flops_per_clip_step(bench.ARCHS["arch_mdm_l"], 196) == 11127660544  # 11.128 GF per clip-step
 
 
@@ -109,3 +115,50 @@ def test_check_ok_logic():
     assert not bench.checks_ok(**dict(good, check={"f16x3": 2e-5}))          # outside the 1e-5 gate
     assert not bench.checks_ok(**dict(good, check={"bf16x3": float("nan")}))  # NaN never passes
     assert bench.checks_ok(finite_by={"bf16": True}, range_flags={}, check={})
+
+
+def test_plain_run_reports_the_headline_only():
+    r = _run(["--gpus", "1"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["check_ok"] is True
+    assert not {"check", "other_dtypes", "cpu_baseline", "torch_rocm_baseline", "power"} & set(j) and j["roofline"] is None
+
+
+def test_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the gathered result of the last timed loop (seed = steps - 1) of all ranks, float32, and the same
+    again on a second run with the same arguments."""
+    import numpy as np
+
+    from oracle import mdm_oracle as O
+
+    dumps = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        r = _run(["--gpus", "2", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert sorted(os.listdir(d)) == ["sample.npy"]
+        dumps.append(np.load(d / "sample.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (6, 99, 1, 8)
+    np.testing.assert_array_equal(dumps[0], O.philox_normal(1, np.arange(6), 1, 99, 8))  # --steps 2: the last timed loop is seed 1
+    np.testing.assert_array_equal(dumps[0], dumps[1])
+
+
+def test_dump_outputs_sample_clips_above_the_cap(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+
+    x = np.arange(40, dtype=np.float64).reshape(10, 4)
+    bench.dump_outputs(str(tmp_path / "all"), {"x": x})
+    np.testing.assert_array_equal(np.load(tmp_path / "all" / "x.npy"), x.astype(np.float32))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "y": -x}, max_bytes=2 * 3 * 4 * 4)  # room for 3 clips of each, float32
+    y = np.load(tmp_path / "a" / "x.npy")
+    assert y.dtype == np.float32 and y.shape == (3, 4)
+    rows = [int(r[0]) // 4 for r in y]
+    assert rows == sorted(set(rows)) and all((y[i] == x[r]).all() for i, r in enumerate(rows))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "y.npy"), -y)  # the same clips of every array
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "x.npy"), y)   # fixed seed: the same clips on every run

@@ -66,7 +66,7 @@ def test_bench_presets_execute_on_the_device(config, dtype, batch):
 
     buf = io.StringIO()
     with redirect_stdout(buf):
-        rc = bench.main(["--gpus", "1", "--config", str(config), "--steps", "1", "--warmup", "1", "--ddpm-steps", "40",
+        rc = bench.main(["--gpus", "1", "--full", "--config", str(config), "--steps", "1", "--warmup", "1", "--ddpm-steps", "40",
                          "--no-cpu-baseline", "--also", ""])
     assert rc == 0
     line = json.loads(buf.getvalue().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 #   kernel_stats_<dtype>.csv       rocprofv3 --kernel-trace --stats summary of a 100-step bench run
 #   hbm_traffic_<dtype>.json       FETCH_SIZE / WRITE_SIZE (separate --pmc passes), per kernel class and launch
 #   step_profile_<dtype>.json      bench.py's in-run HIP-event profile of one step
-#   bench_default.log              the default bench line
+#   bench_default.log              the default bench line with --full (check, roofline, fp32, power, baselines)
 # Pass the commit the tree was built from as TAMF_COMMIT=<sha> (the GPU box has no .git): it is stamped into hbm_traffic_*.json,
 # which bench.py reports as roofline.traffic_source.
 export TMPDIR=/tmp
@@ -61,18 +61,18 @@ json.dump({"command": "rocprofv3 --pmc FETCH_SIZE (and, separately, --pmc WRITE_
            "dtype": dt, "B": 64, "T": 196, "commit": os.environ.get("TAMF_COMMIT", "unstamped"), "csrc_sha16": __import__("bench").csrc_digest(), "kernels": kern}, open(f"{out}/hbm_traffic_{dt}.json", "w"), indent=1)
 PY
   rm -rf $out/pmc_${dt}_FETCH_SIZE $out/pmc_${dt}_WRITE_SIZE
-  python3 bench.py --no-power --steps 1 --warmup 1 --no-cpu-baseline --also "" --fp32-loops 0 --dtype $dt --profile-out $out/step_profile_$dt.json > $out/step_$dt.log 2>&1
+  python3 bench.py --full --no-power --steps 1 --warmup 1 --no-cpu-baseline --also "" --fp32-loops 0 --dtype $dt --profile-out $out/step_profile_$dt.json > $out/step_$dt.log 2>&1
 done
 # the traffic files of THIS tree go where bench.py looks for them (roofline.traffic / traffic_stale) before the bench lines are taken
 mkdir -p profiles/$TAMF_ROUND && cp $out/hbm_traffic_*.json profiles/$TAMF_ROUND/
-timeout 900 python3 bench.py > $out/bench_default.log 2>&1
+timeout 900 python3 bench.py --full > $out/bench_default.log 2>&1
 tail -n 1 $out/bench_default.log | cut -c1-600
 # the clip length the reference's dataset emits (T = 160) and the two 8-GPU presets' per-GPU shards, one line each
 for dt in f16x3 f32 bf16; do
-  timeout 600 python3 bench.py --frames 160 --dtype $dt --also "" --fp32-loops 0 --no-cpu-baseline --steps 2 --warmup 1 > $out/bench_T160_$dt.log 2>&1
+  timeout 600 python3 bench.py --full --frames 160 --dtype $dt --also "" --fp32-loops 0 --no-cpu-baseline --steps 2 --warmup 1 > $out/bench_T160_$dt.log 2>&1
   tail -n 1 $out/bench_T160_$dt.log | cut -c1-200
 done
-timeout 600 python3 bench.py --config 3 --also "" --fp32-loops 0 --no-cpu-baseline --steps 2 --warmup 1 > $out/bench_config3_shard.log 2>&1
-timeout 600 python3 bench.py --config 5 --also "" --fp32-loops 0 --no-cpu-baseline --steps 2 --warmup 1 > $out/bench_config5_shard.log 2>&1
+timeout 600 python3 bench.py --full --config 3 --also "" --fp32-loops 0 --no-cpu-baseline --steps 2 --warmup 1 > $out/bench_config3_shard.log 2>&1
+timeout 600 python3 bench.py --full --config 5 --also "" --fp32-loops 0 --no-cpu-baseline --steps 2 --warmup 1 > $out/bench_config5_shard.log 2>&1
 tail -n 1 $out/bench_config3_shard.log | cut -c1-200; tail -n 1 $out/bench_config5_shard.log | cut -c1-200
 ls $out
