@@ -11,6 +11,7 @@
  *   create_gaussian_diffusion tables   model/diffusion_util.py:5-31, gaussian_diffusion.py:116-161 -> tamf_set_schedule
  *   load_state_dict(torch.load(ckpt))  launch/sample.py:190-192, util/state_util.py:22-39 -> tamf_load_weight / tamf_finalize_weights
  *   SegmentRefineModel.forward trunk   model/segment_refine_model.py:175-217      -> tamf_refine
+ *   SegmentEncoder.forward (FID score) model/segment_encoder.py:16-111            -> tamf_encode
  *
  * Conventions
  *   - plain C types only; every function returns 0 on success or a negative tamf_status; the message of the
@@ -68,7 +69,10 @@ typedef enum tamf_precision {
 
 typedef enum tamf_model_kind {
   TAMF_KIND_G = 0, /* InterationSegmentMDM (5 prefix tokens: t, text, side, shape, obj) */
-  TAMF_KIND_R = 1  /* SegmentRefineModel trunk (3 prefix tokens; h2o distance feature; residual output) */
+  TAMF_KIND_R = 1, /* SegmentRefineModel trunk (3 prefix tokens; h2o distance feature; residual output) */
+  TAMF_KIND_E = 2  /* SegmentEncoder of the FID score (3 prefix tokens + a classification token; tamf_encode only).  fp32 only
+                      (TAMF_PREC_F32); latent_dim 64 with 4 heads, ff_size a multiple of 16 in [16, 512], any num_layers >= 1, max_frames
+                      up to 252; anything else is TAMF_ERR_INVALID.  The G / R entry points return TAMF_ERR_STATE on it. */
 } tamf_model_kind;
 
 /* keys of config/arch_*.yml `model:` (launch/param/model.py:14-87) + the two constants of the modules */
@@ -165,6 +169,20 @@ int tamf_sample_loop(tamf_ctx* ctx, const float* noise_dev, uint64_t seed, int64
  * h2o_dist_dev: (B, T, h2o_dim) f32. */
 int tamf_refine(tamf_ctx* ctx, const float* sample_pose_repr_dev, const float* h2o_dist_dev, float* out_dev,
                 void* stream);
+
+/* SegmentEncoder forward of an E context (segment_encoder.py:77-111; the `batch` dict of the reference, hand_side as device bytes,
+ * 0 = "rh", any other value = "lh" - the Python module raises on anything but "rh" / "lh" as HandsideProcess does):
+ *   pose_repr_dev (B, T, input_dim) f32     shape_dev (B, T, hand_shape_dim) f32     hand_side_dev (B,) uint8
+ *   obj_emb_dev   (B, nobj, obj_embed_dim)  obj_traj_dev (B, nobj, T, obj_input_dim)
+ *   encoding_out_dev (B, latent_dim) f32: the classification-token row after the last layer (the FID feature)
+ *   activation_out_dev (B, input_dim) f32 or NULL: output_process of it
+ * obj_num_host: NULL = the reference's forward on this padded batch (object means over all nobj rows); otherwise (B,) int32 host, each
+ * in [1, nobj]: clip b averages over its first obj_num[b] objects - what the reference's FID script computes, which calls the encoder
+ * with batches of one clip (script/compute_score/compute_score_fid.py:306-349).  No attention mask, as in the reference: frames past
+ * a clip's length take part.  A clip's result does not depend on B or on the other clips, bit for bit. */
+int tamf_encode(tamf_ctx* ctx, int32_t B, int32_t T, int32_t nobj, const int32_t* obj_num_host, const float* pose_repr_dev,
+                const float* shape_dev, const uint8_t* hand_side_dev, const float* obj_emb_dev, const float* obj_traj_dev,
+                float* encoding_out_dev, float* activation_out_dev, void* stream);
 
 /* ---- geometry either side of the trunks ---------------------------- */
 /* Pose decode of launch/sample_refine.py:254-260 / model/segment_refine_model.py:117-124:

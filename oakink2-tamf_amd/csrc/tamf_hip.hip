@@ -30,6 +30,7 @@
 #endif
 #include "tamf_geom.h"
 #include "tamf_misc.h"
+#include "tamf_encoder.h"
 
 // run EXPR with `Op` bound to the operand traits of arithmetic mode `prec` (tamf_precision)
 #define TAMF_WITH_OP(prec, EXPR)                                         \
@@ -132,6 +133,8 @@ struct tamf_ctx {
   unsigned* status = nullptr;  // this context's sticky status word (tamf_device.h): written by its kernels only
   unsigned char* side_dev = nullptr;
   int* objnum_dev = nullptr;  // per-clip object counts of tamf_set_cond_ragged
+  float* enc_w = nullptr;  // SegmentEncoder (TAMF_KIND_E, tamf_encoder.h): packed weights; its prefix rows live in pstatic [Bmax][3][d]
+  int enc_kin = 0;         // ... and the K of its fused input linear map (input_dim + obj_input_dim, padded to 4)
   unsigned host_status = 0;  // status bits raised on the host (TAMF_STATUS_F16_WEIGHT_RANGE at tamf_finalize_weights); never cleared
   std::string weight_note;   // ... and which tensor raised it
   // deferred LayerNorm: partial row statistics of the residual stream after the attention / feed-forward sublayer, [Mmax][d / 32]
@@ -775,10 +778,83 @@ static int alloc_workspaces(tamf_ctx* ctx, int max_batch, int max_frames) {
   return rc;
 }
 
+// ---- SegmentEncoder contexts (TAMF_KIND_E): their own shape set, their own (small) workspaces ----
+static int enc_max_frames(int ff, int kin) {  // the longest clip whose token rows fit the LDS of one CU (tamf_encoder.h)
+  int t = 0;
+  while (t < 5000 && enc_lds_bytes(t + 1 + ENC_P + 1, ff, kin) <= ENC_LDS_BYTES) ++t;
+  return t;
+}
+static int enc_check_shape(const tamf_arch* a, int max_batch, int max_frames) {
+  if (a->latent_dim != ENC_D || a->num_heads != 4)
+    return fail(nullptr, TAMF_ERR_INVALID, "SegmentEncoder (TAMF_KIND_E): latent_dim must be 64 with num_heads 4 (head dim 16)");
+  if (a->ff_size < 16 || a->ff_size > 512 || a->ff_size % 16)
+    return fail(nullptr, TAMF_ERR_INVALID, "SegmentEncoder (TAMF_KIND_E): ff_size must be a multiple of 16 in [16, 512]");
+  if (a->num_layers < 1 || a->num_layers > 64) return fail(nullptr, TAMF_ERR_INVALID, "SegmentEncoder (TAMF_KIND_E): num_layers must be in [1, 64]");
+  if (a->input_dim < 1 || a->input_dim > 128 || a->obj_input_dim < 1 || a->obj_input_dim > 16 || a->hand_shape_dim < 1 ||
+      a->hand_shape_dim > 64 || a->obj_embed_dim < 1 || a->obj_embed_dim > 4096)
+    return fail(nullptr, TAMF_ERR_INVALID, "SegmentEncoder (TAMF_KIND_E): input_dim must be in [1, 128], obj_input_dim in [1, 16], "
+                                           "hand_shape_dim in [1, 64], obj_embed_dim in [1, 4096]");
+  if (max_batch <= 0 || max_batch > (1 << 20) || max_frames <= 0) return fail(nullptr, TAMF_ERR_INVALID, "bad max_batch/max_frames");
+  const int tmax = enc_max_frames(a->ff_size, round_up(a->input_dim + a->obj_input_dim, 4));
+  if (max_frames > tmax)
+    return fail(nullptr, TAMF_ERR_INVALID, "SegmentEncoder (TAMF_KIND_E): max_frames " + std::to_string(max_frames) + " exceeds the limit of " +
+                                               std::to_string(tmax) + " frames (a clip's token rows live in the 160 KiB LDS of one CU)");
+  return 0;
+}
+static int enc_alloc_workspaces(tamf_ctx* ctx, int max_batch, int max_frames) {
+  ctx->Bmax = max_batch;
+  ctx->Tmax = max_frames;
+  ctx->alloc_ws = true;
+  g_alloc_tag = "encoder workspaces";
+  int rc = dev_alloc(ctx, (void**)&ctx->pstatic, (size_t)max_batch * ENC_P * ctx->d * 4, true);
+  if (rc == 0) rc = dev_alloc(ctx, (void**)&ctx->objnum_dev, (size_t)max_batch * 4, true);
+  g_alloc_tag = "(weights / tables)";
+  ctx->alloc_ws = false;
+  return rc;
+}
+static int enc_ctx_create(const tamf_arch* arch, int32_t max_batch, int32_t max_frames, int32_t precision, int32_t device, tamf_ctx** out) {
+  if (precision != TAMF_PREC_F32) return fail(nullptr, TAMF_ERR_INVALID, "SegmentEncoder (TAMF_KIND_E) runs in fp32 only (TAMF_PREC_F32)");
+  if (int rc = enc_check_shape(arch, max_batch, max_frames)) return rc;
+  int ndev = 0;
+  hipError_t de = hipGetDeviceCount(&ndev);
+  if (de != hipSuccess || ndev <= 0)
+    return fail(nullptr, TAMF_ERR_HIP, std::string("no HIP device visible (") + hipGetErrorString(de) + "): libtamf_hip has no CPU fallback");
+  if (device < 0 || device >= ndev) return fail(nullptr, TAMF_ERR_INVALID, "device index out of range");
+  tamf_ctx* ctx = new tamf_ctx();
+  ctx->arch = *arch;
+  ctx->prec = precision;
+  ctx->device = device;
+  ctx->d = arch->latent_dim;
+  ctx->ff = arch->ff_size;
+  ctx->L = arch->num_layers;
+  ctx->H = arch->num_heads;
+  ctx->hd = arch->latent_dim / arch->num_heads;
+  ctx->F = arch->input_dim;
+  ctx->P = ENC_P;
+  ctx->enc_kin = round_up(arch->input_dim + arch->obj_input_dim, 4);
+  auto bail = [&](int rc) {
+    std::string e = ctx->err;
+    tamf_ctx_destroy(ctx);
+    g_noctx_err = e;
+    return rc;
+  };
+  if (hipSetDevice(device) != hipSuccess) return bail(fail(ctx, TAMF_ERR_HIP, "hipSetDevice failed"));
+  hipError_t e = hipFuncSetAttribute((const void*)encoder_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ENC_LDS_BYTES);
+  if (e != hipSuccess) return bail(fail(ctx, TAMF_ERR_HIP, std::string("encoder kernel attribute setup failed: ") + hipGetErrorString(e)));
+  if (int rc = enc_alloc_workspaces(ctx, max_batch, max_frames)) return bail(rc);
+  {
+    std::lock_guard<std::mutex> lk(g_live_mu);
+    g_live_ctx.push_back(ctx);
+  }
+  *out = ctx;
+  return 0;
+}
+
 extern "C" int tamf_ctx_create(const tamf_arch* arch, int32_t max_batch, int32_t max_frames, int32_t precision,
                                int32_t device, tamf_ctx** out) {
   if (!arch || !out) return fail(nullptr, TAMF_ERR_INVALID, "null argument");
   *out = nullptr;
+  if (arch->kind == TAMF_KIND_E) return enc_ctx_create(arch, max_batch, max_frames, precision, device, out);
   const int d = arch->latent_dim;
   if (!(d == 128 || d == 256 || d == 512)) return fail(nullptr, TAMF_ERR_INVALID, "latent_dim must be 128, 256 or 512");
   if (arch->num_heads <= 0 || d % arch->num_heads) return fail(nullptr, TAMF_ERR_INVALID, "bad num_heads");
@@ -915,6 +991,23 @@ static void ws_put(tamf_ctx* c, WorkspaceSet& w) {
 extern "C" int tamf_ctx_resize(tamf_ctx* ctx, int32_t max_batch, int32_t max_frames) {
   TAMF_LAUNCH_LOCK;
   if (!ctx) return fail(ctx, TAMF_ERR_INVALID, "null ctx");
+  if (ctx->arch.kind == TAMF_KIND_E) {  // (no graph, no conditioning: only the prefix rows and object counts are dimensioned)
+    if (int rc = enc_check_shape(&ctx->arch, max_batch, max_frames)) {
+      ctx->err = g_noctx_err;
+      return rc;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    WorkspaceSet old = ws_take(ctx);
+    if (int rc = enc_alloc_workspaces(ctx, max_batch, max_frames)) {
+      WorkspaceSet part = ws_take(ctx);
+      for (void* p : part.ws_allocs) (void)hipFree(p);
+      ws_put(ctx, old);
+      return rc;
+    }
+    for (void* p : old.ws_allocs) (void)hipFree(p);
+    return 0;
+  }
   if (int rc = check_dims(&ctx->arch, max_batch, max_frames)) {
     ctx->err = g_noctx_err;
     return rc;
@@ -955,6 +1048,34 @@ static std::map<std::string, std::vector<int64_t>> expected_shapes(const tamf_ct
     m[n + ".weight"] = {o, i};
     m[n + ".bias"] = {o};
   };
+  if (c->arch.kind == TAMF_KIND_E) {  // SegmentEncoder (segment_encoder.py:16-75): its state-dict key set
+    m["hand_side_process.rh_embed"] = {d};
+    m["hand_side_process.lh_embed"] = {d};
+    lin("hand_shape_process.shape_embed", d, c->arch.hand_shape_dim);
+    lin("obj_embed_process.embedding", d, c->arch.obj_embed_dim);
+    m["classification_token"] = {1, 1, d};
+    lin("input_process.poseEmbedding", d, c->arch.input_dim);
+    lin("obj_input_process.poseEmbedding", d, c->arch.obj_input_dim);
+    lin("input_merge.0", d, 2 * d);
+    lin("input_merge.2", d, d);
+    m["sequence_pos_encoder.pe"] = {5000, 1, d};
+    for (int l = 0; l < c->L; ++l) {
+      const std::string p = "seqTransEncoder.layers." + std::to_string(l);
+      m[p + ".self_attn.in_proj_weight"] = {3 * d, d};
+      m[p + ".self_attn.in_proj_bias"] = {3 * d};
+      lin(p + ".self_attn.out_proj", d, d);
+      lin(p + ".linear1", ff, d);
+      lin(p + ".linear2", d, ff);
+      m[p + ".norm1.weight"] = {d};
+      m[p + ".norm1.bias"] = {d};
+      m[p + ".norm2.weight"] = {d};
+      m[p + ".norm2.bias"] = {d};
+    }
+    lin("output_process.poseFinal.0", d, d);
+    lin("output_process.poseFinal.2", d, d);
+    lin("output_process.poseFinal.4", c->arch.input_dim, d);
+    return m;
+  }
   m["hand_side_process.rh_embed"] = {d};
   m["hand_side_process.lh_embed"] = {d};
   lin("hand_shape_process.shape_embed", d, c->arch.hand_shape_dim);
@@ -1012,6 +1133,84 @@ static int upload_f32(tamf_ctx* ctx, const std::string& name, float** p) {
   return dev_upload(ctx, p, v.data(), v.size());
 }
 
+// SegmentEncoder weights -> the packed layout of tamf_encoder.h (EncHeadOff, then one EncLayerOff block per layer) + the prefix-row
+// tables of prefix_rows_kernel.  The input linear maps are composed in float64 as for G / R: W_in = [W_m1[:, :d] W_p | W_m1[:, d:] W_q].
+static int enc_finalize(tamf_ctx* ctx) {
+  const int d = ctx->d, ff = ctx->ff, F = ctx->F, qd = ctx->arch.obj_input_dim, kin = ctx->enc_kin, hd = ctx->hd, H = ctx->H;
+  auto R = [&](const std::string& n) -> const float* { return ctx->raw.at(n).data(); };
+  const EncHeadOff ho = enc_head_off(kin, F);
+  const EncLayerOff lo = enc_layer_off(ff);
+  std::vector<float> w((size_t)(ho.layers + (long)ctx->L * lo.stride), 0.f);
+  auto put = [&](long off, const std::string& n, size_t cnt) { memcpy(w.data() + off, R(n), cnt * 4); };
+  put(ho.cls, "classification_token", d);
+  {
+    const float *Wm1 = R("input_merge.0.weight"), *bm1 = R("input_merge.0.bias");
+    const float *Wp = R("input_process.poseEmbedding.weight"), *bp = R("input_process.poseEmbedding.bias");
+    const float *Wq = R("obj_input_process.poseEmbedding.weight"), *bq = R("obj_input_process.poseEmbedding.bias");
+    for (int n = 0; n < d; ++n) {
+      double acc_b = bm1[n];
+      for (int j = 0; j < d; ++j) acc_b += (double)Wm1[(size_t)n * 2 * d + j] * bp[j] + (double)Wm1[(size_t)n * 2 * d + d + j] * bq[j];
+      w[ho.bin + n] = (float)acc_b;
+      for (int k = 0; k < F; ++k) {
+        double a = 0;
+        for (int j = 0; j < d; ++j) a += (double)Wm1[(size_t)n * 2 * d + j] * Wp[(size_t)j * F + k];
+        w[ho.win + (long)n * kin + k] = (float)a;
+      }
+      for (int k = 0; k < qd; ++k) {
+        double a = 0;
+        for (int j = 0; j < d; ++j) a += (double)Wm1[(size_t)n * 2 * d + d + j] * Wq[(size_t)j * qd + k];
+        w[ho.win + (long)n * kin + F + k] = (float)a;
+      }
+    }
+  }
+  put(ho.wm2, "input_merge.2.weight", (size_t)d * d);
+  put(ho.bm2, "input_merge.2.bias", d);
+  put(ho.p0, "output_process.poseFinal.0.weight", (size_t)d * d);
+  put(ho.pb0, "output_process.poseFinal.0.bias", d);
+  put(ho.p2, "output_process.poseFinal.2.weight", (size_t)d * d);
+  put(ho.pb2, "output_process.poseFinal.2.bias", d);
+  put(ho.p4, "output_process.poseFinal.4.weight", (size_t)F * d);
+  put(ho.pb4, "output_process.poseFinal.4.bias", F);
+  for (int l = 0; l < ctx->L; ++l) {
+    const std::string p = "seqTransEncoder.layers." + std::to_string(l);
+    const long base = ho.layers + (long)l * lo.stride;
+    const float *Win = R(p + ".self_attn.in_proj_weight"), *bin = R(p + ".self_attn.in_proj_bias");
+    for (int h = 0; h < H; ++h)  // rows grouped per head: [q_h | k_h | v_h]
+      for (int part = 0; part < 3; ++part)
+        for (int j = 0; j < hd; ++j) {
+          const int dst = h * 3 * hd + part * hd + j, src = part * d + h * hd + j;
+          memcpy(w.data() + base + lo.wqkv + (long)dst * d, Win + (size_t)src * d, (size_t)d * 4);
+          w[base + lo.bqkv + dst] = bin[src];
+        }
+    put(base + lo.wo, p + ".self_attn.out_proj.weight", (size_t)d * d);
+    put(base + lo.bo, p + ".self_attn.out_proj.bias", d);
+    put(base + lo.w1, p + ".linear1.weight", (size_t)ff * d);
+    put(base + lo.b1, p + ".linear1.bias", ff);
+    put(base + lo.w2, p + ".linear2.weight", (size_t)d * ff);
+    put(base + lo.b2, p + ".linear2.bias", d);
+    put(base + lo.g1, p + ".norm1.weight", d);
+    put(base + lo.be1, p + ".norm1.bias", d);
+    put(base + lo.g2, p + ".norm2.weight", d);
+    put(base + lo.be2, p + ".norm2.bias", d);
+  }
+  TRY(dev_upload(ctx, &ctx->enc_w, w.data(), w.size()));
+  TRY(upload_f32(ctx, "sequence_pos_encoder.pe", &ctx->pe));
+  auto upload_T = [&](const std::string& name, int N, int K, float** p) -> int {  // W [N][K] -> W^T [K][N] (prefix_rows_kernel)
+    const float* W = R(name);
+    std::vector<float> t((size_t)N * K);
+    for (int n = 0; n < N; ++n)
+      for (int k = 0; k < K; ++k) t[(size_t)k * N + n] = W[(size_t)n * K + k];
+    return dev_upload(ctx, p, t.data(), t.size());
+  };
+  TRY(upload_T("hand_shape_process.shape_embed.weight", d, ctx->arch.hand_shape_dim, &ctx->WshapeT));
+  TRY(upload_f32(ctx, "hand_shape_process.shape_embed.bias", &ctx->bshape));
+  TRY(upload_T("obj_embed_process.embedding.weight", d, ctx->arch.obj_embed_dim, &ctx->WobjT));
+  TRY(upload_f32(ctx, "obj_embed_process.embedding.bias", &ctx->bobj));
+  TRY(upload_f32(ctx, "hand_side_process.rh_embed", &ctx->rh));
+  TRY(upload_f32(ctx, "hand_side_process.lh_embed", &ctx->lh));
+  return 0;
+}
+
 extern "C" int tamf_finalize_weights(tamf_ctx* ctx, int32_t max_timesteps, void* stream) {
   TAMF_LAUNCH_LOCK;
   if (!ctx) return fail(ctx, TAMF_ERR_INVALID, "null ctx");
@@ -1021,6 +1220,12 @@ extern "C" int tamf_finalize_weights(tamf_ctx* ctx, int32_t max_timesteps, void*
   hipStream_t st = (hipStream_t)stream;
   for (const auto& kv : expected_shapes(ctx))
     if (!ctx->raw.count(kv.first)) return fail(ctx, TAMF_ERR_MISSING, "missing checkpoint tensor: " + kv.first);
+  if (ctx->arch.kind == TAMF_KIND_E) {
+    TRY(enc_finalize(ctx));
+    ctx->raw.clear();
+    ctx->finalized = true;
+    return 0;
+  }
   const int d = ctx->d, ff = ctx->ff, F = ctx->F, prec = ctx->prec;
   auto R = [&](const std::string& n) -> const float* { return ctx->raw.at(n).data(); };
 
@@ -1194,6 +1399,7 @@ static int retire_graph(tamf_ctx* ctx) {
 
 extern "C" int tamf_set_schedule(tamf_ctx* ctx, int32_t n_steps, const double* c1, const double* c2, const double* logvar) {
   TAMF_LAUNCH_LOCK;
+  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
   if (!ctx || !c1 || !c2 || !logvar || n_steps <= 0) return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   ctx->h_c1.resize(n_steps);
@@ -1279,6 +1485,7 @@ extern "C" int tamf_set_cond_ragged(tamf_ctx* ctx, int32_t B, int32_t T, int32_t
                                     const float* text_emb_dev, const uint8_t* hand_side_host, const float* shape_dev,
                                     const float* obj_emb_dev, const float* obj_traj_dev, void* stream) {
   TAMF_LAUNCH_LOCK;
+  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
   if (!ctx) return fail(ctx, TAMF_ERR_INVALID, "null ctx");
   if (!ctx->finalized) return fail(ctx, TAMF_ERR_STATE, "weights not finalised");
   if (B <= 0 || B > ctx->Bmax || T <= 0 || T > ctx->Tmax || nobj <= 0) return fail(ctx, TAMF_ERR_INVALID, "B/T/nobj out of range");
@@ -1568,6 +1775,7 @@ static int denoise_impl(tamf_ctx* ctx, const float* x, const int64_t* t_dev, flo
 
 extern "C" int tamf_denoise(tamf_ctx* ctx, const float* x_dev, const int64_t* t_dev, float* x0_out_dev, void* stream) {
   TAMF_LAUNCH_LOCK;
+  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
   if (!ctx || !x_dev || !t_dev || !x0_out_dev) return fail(ctx, TAMF_ERR_INVALID, "null argument");
   if (!ctx->cond_set) return fail(ctx, TAMF_ERR_STATE, "conditioning not set");
   if (ctx->arch.kind != TAMF_KIND_G) return fail(ctx, TAMF_ERR_STATE, "tamf_denoise needs a G context");
@@ -1594,6 +1802,7 @@ static int refine_impl(tamf_ctx* ctx, const float* x_in, const float* h2o, float
 extern "C" int tamf_refine(tamf_ctx* ctx, const float* sample_pose_repr_dev, const float* h2o_dist_dev, float* out_dev,
                            void* stream) {
   TAMF_LAUNCH_LOCK;
+  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
   if (!ctx || !sample_pose_repr_dev || !h2o_dist_dev || !out_dev) return fail(ctx, TAMF_ERR_INVALID, "null argument");
   if (!ctx->cond_set) return fail(ctx, TAMF_ERR_STATE, "conditioning not set");
   if (ctx->arch.kind != TAMF_KIND_R) return fail(ctx, TAMF_ERR_STATE, "tamf_refine needs an R context");
@@ -1605,6 +1814,7 @@ extern "C" int tamf_refine(tamf_ctx* ctx, const float* sample_pose_repr_dev, con
 
 extern "C" int tamf_ddpm_step(tamf_ctx* ctx, const float* x_t_dev, const float* x0_dev, int32_t t, const float* noise_dev,
                               float* x_out_dev, int64_t n, void* stream) {
+  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
   if (!ctx || !x_t_dev || !x0_dev || !x_out_dev || n <= 0) return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
   if (ctx->n_steps <= 0) return fail(ctx, TAMF_ERR_STATE, "schedule not set");
   if (t < 0 || t >= ctx->n_steps) return fail(ctx, TAMF_ERR_INVALID, "t out of range");
@@ -1698,6 +1908,7 @@ static int loop_impl(tamf_ctx* ctx, const float* noise, uint64_t seed, int64_t c
 extern "C" int tamf_sample_loop(tamf_ctx* ctx, const float* noise_dev, uint64_t seed, int64_t clip_id_base, float* x0_out_dev,
                                 float* dump_dev, int32_t use_graph, void* stream) {
   TAMF_LAUNCH_LOCK;
+  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
   if (!ctx || !x0_out_dev) return fail(ctx, TAMF_ERR_INVALID, "null argument");
   if (!ctx->cond_set) return fail(ctx, TAMF_ERR_STATE, "conditioning not set");
   if (ctx->n_steps <= 0) return fail(ctx, TAMF_ERR_STATE, "schedule not set");
@@ -1710,6 +1921,7 @@ extern "C" int tamf_sample_loop(tamf_ctx* ctx, const float* noise_dev, uint64_t 
 }
 
 extern "C" int tamf_get_status_flags(tamf_ctx* ctx, uint32_t* flags, int32_t clear, void* stream) {
+  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
   if (!ctx || !flags) return fail(ctx, TAMF_ERR_INVALID, "null argument");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream));
@@ -1851,6 +2063,7 @@ static int profile_run(tamf_ctx* ctx, int32_t max_n, float* ms_host, double* flo
 extern "C" int tamf_step_profile(tamf_ctx* ctx, int32_t max_n, float* ms_host, double* flops_host, char* names_host,
                                  void* stream) {
   TAMF_LAUNCH_LOCK;
+  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
   if (!ctx || !ms_host || !flops_host || !names_host || max_n <= 0) return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
   if (!ctx->cond_set || ctx->n_steps <= 0) return fail(ctx, TAMF_ERR_STATE, "conditioning / schedule not set");
   if (ctx->arch.kind != TAMF_KIND_G) return fail(ctx, TAMF_ERR_STATE, "needs a G context");
@@ -1867,6 +2080,7 @@ extern "C" int tamf_step_profile(tamf_ctx* ctx, int32_t max_n, float* ms_host, d
 extern "C" int tamf_refine_profile(tamf_ctx* ctx, const float* sample_pose_repr_dev, const float* h2o_dist_dev, float* out_dev,
                                    int32_t max_n, float* ms_host, double* flops_host, char* names_host, void* stream) {
   TAMF_LAUNCH_LOCK;
+  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
   if (!ctx || !sample_pose_repr_dev || !h2o_dist_dev || !out_dev || !ms_host || !flops_host || !names_host || max_n <= 0)
     return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
   if (!ctx->cond_set) return fail(ctx, TAMF_ERR_STATE, "conditioning not set");
@@ -2226,6 +2440,50 @@ extern "C" int tamf_bench_gemm(int32_t precision, int32_t epi_kind, int32_t krot
 // ------------------------------------------------------------------------------------------------
 // geometry either side of the trunks
 // ------------------------------------------------------------------------------------------------
+// ------------------------------------------------------------------------------------------------
+// SegmentEncoder forward (TAMF_KIND_E): two launches - the prefix rows (prefix_rows_kernel, shared with G / R) and the encoder
+// (encoder_kernel, tamf_encoder.h: one workgroup per clip)
+// ------------------------------------------------------------------------------------------------
+extern "C" int tamf_encode(tamf_ctx* ctx, int32_t B, int32_t T, int32_t nobj, const int32_t* obj_num_host, const float* pose_repr_dev,
+                           const float* shape_dev, const uint8_t* hand_side_dev, const float* obj_emb_dev, const float* obj_traj_dev,
+                           float* encoding_out_dev, float* activation_out_dev, void* stream) {
+  TAMF_LAUNCH_LOCK;
+  if (!ctx) return fail(ctx, TAMF_ERR_INVALID, "null ctx");
+  if (ctx->arch.kind != TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, "tamf_encode needs a SegmentEncoder (TAMF_KIND_E) context");
+  if (!ctx->finalized) return fail(ctx, TAMF_ERR_STATE, "weights not finalised");
+  if (B <= 0 || B > ctx->Bmax || T <= 0 || T > ctx->Tmax || nobj <= 0)
+    return fail(ctx, TAMF_ERR_INVALID, "B/T/nobj out of range (B = " + std::to_string(B) + " of max_batch " + std::to_string(ctx->Bmax) +
+                                           ", T = " + std::to_string(T) + " of max_frames " + std::to_string(ctx->Tmax) + ")");
+  if (!pose_repr_dev || !shape_dev || !hand_side_dev || !obj_emb_dev || !obj_traj_dev || !encoding_out_dev)
+    return fail(ctx, TAMF_ERR_INVALID, "null tensor");
+  if (obj_num_host)
+    for (int b = 0; b < B; ++b)
+      if (obj_num_host[b] < 1 || obj_num_host[b] > nobj)
+        return fail(ctx, TAMF_ERR_INVALID, "obj_num[" + std::to_string(b) + "] = " + std::to_string(obj_num_host[b]) + " outside [1, nobj]");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int* cnt = nullptr;
+  if (obj_num_host) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->objnum_dev, obj_num_host, sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
+    cnt = ctx->objnum_dev;
+  }
+  const int d = ctx->d, sd = ctx->arch.hand_shape_dim, od = ctx->arch.obj_embed_dim;
+  PrefixArgs pa{};
+  pa.side = hand_side_dev; pa.rh = ctx->rh; pa.lh = ctx->lh;
+  pa.shape = shape_dev; pa.WshapeT = ctx->WshapeT; pa.bshape = ctx->bshape;
+  pa.oemb = obj_emb_dev; pa.WobjT = ctx->WobjT; pa.bobj = ctx->bobj; pa.cnt = cnt;
+  pa.pe = ctx->pe; pa.pstatic = ctx->pstatic;
+  pa.B = B; pa.d = d; pa.T = T; pa.sd = sd; pa.nobj = nobj; pa.od = od; pa.clip_dim = 0; pa.nrows = ENC_P; pa.ht = 0;
+  hipLaunchKernelGGL(prefix_rows_kernel, dim3(B, ENC_P), dim3(1024), (size_t)(std::max(od, sd) + 1024) * sizeof(float), st, pa);
+  EncArgs ea{};
+  ea.w = ctx->enc_w; ea.pe = ctx->pe; ea.pstatic = ctx->pstatic; ea.pose = pose_repr_dev; ea.traj = obj_traj_dev; ea.cnt = cnt;
+  ea.enc = encoding_out_dev; ea.act = activation_out_dev;
+  ea.T = T; ea.nobj = nobj; ea.F = ctx->F; ea.qd = ctx->arch.obj_input_dim; ea.kin = ctx->enc_kin; ea.ff = ctx->ff; ea.L = ctx->L;
+  hipLaunchKernelGGL(encoder_kernel, dim3(B), dim3(ENC_NT), (size_t)enc_lds_bytes(T + ENC_P + 1, ctx->ff, ctx->enc_kin), st, ea);
+  HIPCHK(ctx, hipGetLastError());
+  return 0;
+}
+
 extern "C" int tamf_pose_decode(const float* pose_repr_dev, int64_t n_frames, int32_t n_joints, float* tsl_out_dev,
                                 float* quat_out_dev, void* stream) {
   if (!pose_repr_dev || !quat_out_dev || n_frames <= 0 || n_joints <= 0) return fail(nullptr, TAMF_ERR_INVALID, "bad argument");

@@ -11,7 +11,7 @@ import torch
 from . import _lib
 
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x3": 2, "f16x3": 3}
-KINDS = {"G": 0, "R": 1}
+KINDS = {"G": 0, "R": 1, "E": 2}  # E: the SegmentEncoder of the FID score (fp32 only)
 
 
 class TamfError(RuntimeError):
@@ -70,6 +70,8 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.tamf_ddpm_step.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p]
     L.tamf_sample_loop.argtypes = [c_void_p, c_void_p, c_uint64, c_int64, c_void_p, c_void_p, c_int32, c_void_p]
     L.tamf_refine.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    if hasattr(L, "tamf_encode"):  # (absent from older A/B builds)
+        L.tamf_encode.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p] + [c_void_p] * 8
     if hasattr(L, "tamf_get_status_flags"):  # (absent only from older A/B builds loaded by tools/ through _lib.load_from)
         L.tamf_get_status_flags.argtypes = [c_void_p, POINTER(ctypes.c_uint32), c_int32, c_void_p]
     L.tamf_step_kernel_count.argtypes = [c_void_p]
@@ -170,11 +172,13 @@ def require_gpu(device=None) -> torch.device:
 class TamfContext:
     """One library context = one (model, device, precision, max batch, max frames)."""
 
-    def __init__(self, arch: Mapping[str, int], max_batch: int, max_frames: int, precision: str = DEFAULT_PRECISION,
+    def __init__(self, arch: Mapping[str, int], max_batch: int, max_frames: int, precision: Optional[str] = None,
                  device=None, kind: str = "G", range_check: bool = False):
         """range_check=True: `denoise`, `sample_loop` and `refine` read this context's status word after the call (one stream
         synchronisation) and raise TamfRangeError when an activation left the fp16 range (f16x3 only).  The drop-in modules do
         their own check - with an f32 fallback - and leave this off; a raw context has no fallback."""
+        if precision is None:  # (the encoder, kind "E", has one arithmetic mode: fp32)
+            precision = "f32" if kind == "E" else DEFAULT_PRECISION
         self.device = require_gpu(device)
         self._L = lib()  # the library this context lives in: libtamf_hip.so unless a test / tool switched to the hooks build
         self.precision = precision
@@ -194,6 +198,7 @@ class TamfContext:
             kind=KINDS[kind],
         )
         self.input_dim = a.input_dim
+        self.latent_dim = a.latent_dim
         self.h2o_dim = a.h2o_dim
         self.max_batch, self.max_frames = int(max_batch), int(max_frames)
         self._h = c_void_p()
@@ -310,6 +315,38 @@ class TamfContext:
                                       c_void_p(_stream_ptr(dev))), self._h)
         self._raise_on_range()
         return out
+
+    def encode(self, pose_repr: torch.Tensor, shape: torch.Tensor, hand_side: Sequence, obj_embedding: torch.Tensor,
+               obj_traj: torch.Tensor, obj_num: Optional[Sequence[int]] = None, with_activation: bool = True):
+        """SegmentEncoder forward of an E context (tamf_encode): pose_repr (B, T, input_dim), shape (B, T, 10), hand_side B x "rh"/"lh",
+        obj_embedding (B, nobj, 768), obj_traj (B, nobj, T, 9) -> (encoding (B, latent_dim), activation (B, input_dim) or None).
+        obj_num: per-clip object counts (the reference FID script's batches of one clip); None: means over all nobj rows."""
+        if self.kind != "E":
+            raise TamfError(f"encode needs a SegmentEncoder context (kind 'E'), this one is kind {self.kind!r}")
+        side = [hand_side_code(hs) for hs in hand_side]
+        dev = self.device
+        pr, sh, oe, ot = _dev_f32(pose_repr, dev), _dev_f32(shape, dev), _dev_f32(obj_embedding, dev), _dev_f32(obj_traj, dev)
+        B, T, F = pr.shape
+        nobj = ot.shape[1]
+        if F != self.input_dim or tuple(sh.shape[:2]) != (B, T) or tuple(oe.shape[:2]) != (B, nobj) or tuple(ot.shape[:3]) != (B, nobj, T) \
+                or len(side) != B:
+            raise ValueError(f"inconsistent encoder inputs: pose_repr {tuple(pr.shape)}, shape {tuple(sh.shape)}, obj_embedding "
+                             f"{tuple(oe.shape)}, obj_traj {tuple(ot.shape)}, {len(side)} hand sides")
+        num_np = None
+        if obj_num is not None:
+            num_np = np.ascontiguousarray(torch.as_tensor(obj_num).cpu().numpy() if isinstance(obj_num, torch.Tensor) else obj_num, dtype=np.int32)
+            if num_np.shape != (B,):
+                raise ValueError(f"obj_num must hold one count per clip: shape {num_np.shape} for B = {B}")
+        side_d = torch.tensor(side, dtype=torch.uint8, device=dev)
+        enc = torch.empty(B, self.latent_dim, dtype=torch.float32, device=dev)
+        act = torch.empty(B, F, dtype=torch.float32, device=dev) if with_activation else None
+        with torch.cuda.device(dev):
+            _check(self._L.tamf_encode(self._h, B, T, nobj, num_np.ctypes.data_as(c_void_p) if num_np is not None else c_void_p(0),
+                                       c_void_p(pr.data_ptr()), c_void_p(sh.data_ptr()), c_void_p(side_d.data_ptr()), c_void_p(oe.data_ptr()),
+                                       c_void_p(ot.data_ptr()), c_void_p(enc.data_ptr()), c_void_p(act.data_ptr() if act is not None else 0),
+                                       c_void_p(_stream_ptr(dev))), self._h, self._L)
+        self._keep = [pr, sh, oe, ot, side_d]
+        return enc, act
 
     def ddpm_step(self, x_t: torch.Tensor, x0: torch.Tensor, t: int, noise: Optional[torch.Tensor]) -> torch.Tensor:
         dev = self.device

@@ -35,7 +35,12 @@ def write_sample_npy(ckpt: str, offset: str, sample_id: int, pose_repr: np.ndarr
 
 
 def refine_sample_path(ckpt: str, offset: str, info: Sequence) -> str:
-    return os.path.join(ckpt, "sample", offset, str(info[0]).replace("/", "++"), str(info[1]), str(info[2]), "save_dict.pkl")
+    return refine_sample_path_in(os.path.join(ckpt, "sample", offset), info)
+
+
+def refine_sample_path_in(sample_dir: str, info: Sequence) -> str:
+    """the save_dict.pkl of clip `info` under <ckpt_path>/sample/<offset> (compute_score_fid.py's --debug.sample_refine_filepath)"""
+    return os.path.join(sample_dir, str(info[0]).replace("/", "++"), str(info[1]), str(info[2]), "save_dict.pkl")
 
 
 def build_refine_save_dict(info: Sequence, hand_side: str, joints, verts, faces, obj_list, avai_len, frame_id,

@@ -1,0 +1,1 @@
+"""Evaluation metrics of the reference's README ("Evaluation"): FID over SegmentEncoder features (fid.py)."""
