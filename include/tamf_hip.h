@@ -12,6 +12,7 @@
  *   load_state_dict(torch.load(ckpt))  launch/sample.py:190-192, util/state_util.py:22-39 -> tamf_load_weight / tamf_finalize_weights
  *   SegmentRefineModel.forward trunk   model/segment_refine_model.py:175-217      -> tamf_refine
  *   SegmentEncoder.forward (FID score) model/segment_encoder.py:16-111            -> tamf_encode
+ *   PSKL-J spectra (score script)      script/compute_score/compute_score_psklj.py:270-305 -> tamf_power_spectrum_sum
  *
  * Conventions
  *   - plain C types only; every function returns 0 on success or a negative tamf_status; the message of the
@@ -230,6 +231,19 @@ int tamf_vertex_normals(const float* verts_dev, int64_t n_mesh, int32_t V, const
 int tamf_mesh_contains(const double* verts_dev, const int32_t* faces_dev, int32_t n_faces, const double* points_dev,
                        int64_t n_points, const double* scale3, const double* translate3, int32_t resolution,
                        double* tri_workspace_dev, uint8_t* contains_out_dev, void* stream);
+
+/* Summed power spectrum of joint accelerations, the device half of the PSKL-J score (script/compute_score/compute_score_psklj.py:
+ * 270-271 tail hold, 280-285 np.diff(n=2) / np.fft.fft / |.|^2 per clip, 305 the sum over clips; 306-316 - epsilon, normalisation, the
+ * two KL sums - stay on the host, oakink2_tamf_amd.metrics.psklj.pskl_terms):
+ *   joints_dev (N, T, F) f32 (F = 63: 21 joints x 3)     len_host (N,) int32 HOST, each in [1, T], or NULL = all T frames valid
+ *   psd_sum_dev (T-2, F) f64: accumulate = 0 overwrites it, 1 adds onto what it holds     psd_clip_dev (N, T-2, F) f64 or NULL
+ * Frames t >= len[n] take the value of frame len[n]-1; the two differences are float32 subtractions in numpy's order (bit-equal
+ * accelerations); the DFT of length T-2 is direct, in float64, with table twiddles indexed by (k*n) mod (T-2).  The clips are added
+ * in the order n = 0 .. N-1 for every (k, f), without atomics: the bits of psd_sum depend neither on launch geometry nor on how a set
+ * of clips is split over consecutive calls with accumulate = 1.  3 <= T <= 512 (LDS); anything else is TAMF_ERR_INVALID and launches
+ * nothing. */
+int tamf_power_spectrum_sum(const float* joints_dev, const int32_t* len_host, int32_t N, int32_t T, int32_t F, int32_t accumulate,
+                            double* psd_sum_dev, double* psd_clip_dev, void* stream);
 
 /* Range guard of the split-fp16 mode.  The reference computes in fp32 (launch/sample.py:173); TAMF_PREC_F16X3 stores every
  * MFMA operand as two fp16 planes, so an ACTIVATION beyond +-65504 cannot be represented (weights are pre-scaled per tensor by a

@@ -31,6 +31,7 @@
 #include "tamf_geom.h"
 #include "tamf_misc.h"
 #include "tamf_encoder.h"
+#include "tamf_spectrum.h"
 
 // run EXPR with `Op` bound to the operand traits of arithmetic mode `prec` (tamf_precision)
 #define TAMF_WITH_OP(prec, EXPR)                                         \
@@ -2562,6 +2563,50 @@ extern "C" int tamf_mesh_contains(const double* verts_dev, const int32_t* faces_
                      (long)n_points, scale3[0], scale3[1], scale3[2], translate3[0], translate3[1], translate3[2],
                      (double)resolution, contains_out_dev);
   hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(nullptr, TAMF_ERR_HIP, hipGetErrorString(e));
+  return 0;
+}
+
+// PSKL-J score, device half (tamf_spectrum.h): one launch per PS_LENS clips - the lengths travel in the kernel arguments - each
+// continuing the sums of the one before, which by the kernel's ordered addition is the same arithmetic as one launch over all N
+extern "C" int tamf_power_spectrum_sum(const float* joints_dev, const int32_t* len_host, int32_t N, int32_t T, int32_t F,
+                                       int32_t accumulate, double* psd_sum_dev, double* psd_clip_dev, void* stream) {
+  if (N < 1 || F < 1) return fail(nullptr, TAMF_ERR_INVALID, "bad shape (N = " + std::to_string(N) + ", F = " + std::to_string(F) + ")");
+  if (T < 3) return fail(nullptr, TAMF_ERR_INVALID, "T = " + std::to_string(T) + ": the second difference needs at least 3 frames");
+  if (T > PS_MAX_T)
+    return fail(nullptr, TAMF_ERR_INVALID, "T = " + std::to_string(T) + " above the " + std::to_string(PS_MAX_T) +
+                                               " frames whose accelerations and twiddle table fit the LDS");
+  if (!joints_dev || !psd_sum_dev) return fail(nullptr, TAMF_ERR_INVALID, "null argument");
+  if (len_host)
+    for (int n = 0; n < N; ++n)
+      if (len_host[n] < 1 || len_host[n] > T)
+        return fail(nullptr, TAMF_ERR_INVALID, "len[" + std::to_string(n) + "] = " + std::to_string(len_host[n]) + " outside [1, T]");
+  const int L = T - 2, K = L / 2 + 1;
+  const size_t lds = ps_lds_bytes(L);
+  // the dynamic-LDS ceiling of the kernel is raised once per device, to what the longest accepted clip needs
+  static std::atomic<uint64_t> attr_set{0};
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return fail(nullptr, TAMF_ERR_HIP, std::string("hipGetDevice: ") + hipGetErrorString(e));
+  const uint64_t dev_bit = (dev >= 0 && dev < 64) ? (uint64_t)1 << dev : 0;
+  if (!(attr_set.load() & dev_bit) || !dev_bit) {
+    e = hipFuncSetAttribute((const void*)power_spectrum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)ps_lds_bytes(PS_MAX_T - 2));
+    if (e != hipSuccess) return fail(nullptr, TAMF_ERR_HIP, std::string("power spectrum kernel attribute setup failed: ") + hipGetErrorString(e));
+    attr_set.fetch_or(dev_bit);
+  }
+  const dim3 grid((F + PS_FT - 1) / PS_FT, (K + PS_KT - 1) / PS_KT);
+  PsLens lens;  // refilled per launch up to its n; what a longer earlier launch left beyond n is never read (the kernel stops at n)
+  memset(&lens, 0, sizeof(lens));
+  for (int n0 = 0; n0 < N; n0 += PS_LENS) {
+    const int n = std::min(PS_LENS, N - n0);
+    if (len_host)
+      for (int i = 0; i < n; ++i) lens.v[i] = (uint16_t)len_host[n0 + i];
+    hipLaunchKernelGGL(power_spectrum_kernel, grid, dim3(PS_NT), lds, (hipStream_t)stream, joints_dev + (size_t)n0 * T * F, lens,
+                       len_host ? 1 : 0, n, T, F, (accumulate || n0 > 0) ? 1 : 0, psd_sum_dev,
+                       psd_clip_dev ? psd_clip_dev + (size_t)n0 * L * F : nullptr);
+  }
+  e = hipGetLastError();
   if (e != hipSuccess) return fail(nullptr, TAMF_ERR_HIP, hipGetErrorString(e));
   return 0;
 }
