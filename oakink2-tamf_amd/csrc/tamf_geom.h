@@ -2,6 +2,7 @@
 // unit quaternion) and the hand-vertex -> nearest object point distance feature of the refiner.  fp32, VALU-bound.
 #pragma once
 #include "tamf_device.h"
+#include "tamf_mesh.h"
 
 TAMF_DEV void gs_rows(const float* a, float (&r)[9]) {
   // Gram-Schmidt of (a[0..2], a[3..5]); rows of the rotation matrix = b1, b2, b1 x b2
@@ -139,37 +140,6 @@ __global__ __launch_bounds__(256) void h2o_dist_kernel(const float* __restrict__
 // reference's operation order and no fused multiply-adds, so that the booleans are bit-identical to numpy's.
 // Per triangle (rescaled to the 512-grid frame) 16 doubles are prepared once: t3.xy, the 2D edge matrix a00 a01 a10 a11,
 // sign/abs of its determinant, the normal's x, y, sign/abs of its z, t1.xy and t1.z * |n_z|.
-constexpr int MESH_TC = 16;
-__global__ void mesh_prepare_kernel(const double* __restrict__ verts, const int* __restrict__ faces, int F, double sx, double sy,
-                                    double sz, double tx, double ty, double tz, double* __restrict__ tc) {
-#pragma clang fp contract(off)
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= F) return;
-  double t[3][3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double* v = verts + (long)faces[f * 3 + k] * 3;
-    t[k][0] = sx * v[0] + tx;
-    t[k][1] = sy * v[1] + ty;
-    t[k][2] = sz * v[2] + tz;
-  }
-  const double a00 = t[0][0] - t[2][0], a01 = t[1][0] - t[2][0], a10 = t[0][1] - t[2][1], a11 = t[1][1] - t[2][1];
-  const double det = a00 * a11 - a01 * a10;
-  const double v1x = t[2][0] - t[0][0], v1y = t[2][1] - t[0][1], v1z = t[2][2] - t[0][2];
-  const double v2x = t[1][0] - t[0][0], v2y = t[1][1] - t[0][1], v2z = t[1][2] - t[0][2];
-  const double nx = v1y * v2z - v1z * v2y, ny = v1z * v2x - v1x * v2z, nz = v1x * v2y - v1y * v2x;
-  const double an = fabs(nz), sn = nz > 0.0 ? 1.0 : (nz < 0.0 ? -1.0 : 0.0);
-  double* o = tc + (long)f * MESH_TC;
-  o[0] = t[2][0]; o[1] = t[2][1];
-  o[2] = a00; o[3] = a01; o[4] = a10; o[5] = a11;
-  o[6] = det > 0.0 ? 1.0 : (det < 0.0 ? -1.0 : 0.0);
-  o[7] = fabs(det);
-  o[8] = nx; o[9] = ny; o[10] = sn; o[11] = an;
-  o[12] = t[0][0]; o[13] = t[0][1];
-  o[14] = t[0][2] * an;
-  o[15] = 0.0;
-}
-
 __global__ __launch_bounds__(256) void mesh_contains_kernel(const double* __restrict__ tc, int F, const double* __restrict__ pts,
                                                             long N, double sx, double sy, double sz, double tx, double ty,
                                                             double tz, double res, unsigned char* __restrict__ out) {

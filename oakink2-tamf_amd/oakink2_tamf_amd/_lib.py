@@ -1,5 +1,6 @@
 """Locate / build / load libtamf_hip.so (the C-ABI of include/tamf_hip.h) and, for tests/ and tools/ only, libtamf_hip_hooks.so
-(the same sources with -DTAMF_TEST_HOOKS: + the entry points of include/tamf_hip_test.h)."""
+(the same sources with -DTAMF_TEST_HOOKS: + the entry points of include/tamf_hip_test.h); and libtamf_eval.so (include/tamf_eval.h:
+the context-free evaluation kernels of the SIV score), a library of its own with its own sources, stamp and load_eval()."""
 from __future__ import annotations
 
 import ctypes
@@ -14,11 +15,34 @@ INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "..", "include"))
 LIB_PATH = os.path.join(_HERE, "lib", "libtamf_hip.so")
 HOOKS_PATH = os.path.join(_HERE, "lib", "libtamf_hip_hooks.so")  # test / measurement build (never loaded by the product path)
 HEADERS = ("tamf_hip.h", "tamf_hip_test.h")
-SOURCES = [f for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h"))] if os.path.isdir(CSRC) else []
+EVAL_LIB_PATH = os.path.join(_HERE, "lib", "libtamf_eval.so")
+EVAL_HEADERS = ("tamf_eval.h", "tamf_hip.h")  # (tamf_hip.h for the tamf_status enum)
+EVAL_ONLY = ("tamf_eval.hip", "tamf_voxel.h")  # sources of libtamf_eval.so alone: the sampler libraries neither compile nor stamp them
+
+
+def _include_closure(root: str):
+    """root and every csrc header it includes with #include "...", transitively: what a build of `root` reads from csrc/"""
+    import re
+
+    seen, todo = [], [root]
+    while todo:
+        name = todo.pop()
+        path = os.path.join(CSRC, name)
+        if name in seen or not os.path.exists(path):
+            continue
+        seen.append(name)
+        with open(path) as f:
+            todo += [m for m in re.findall(r'^\s*#\s*include\s+"([^"/]+)"', f.read(), flags=re.M)]
+    return sorted(seen)
+
+
+EVAL_SOURCES = _include_closure("tamf_eval.hip")  # tamf_eval.hip, tamf_voxel.h and the headers those include (tamf_mesh.h, tamf_device.h)
+SOURCES = [f for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h")) and f not in EVAL_ONLY] if os.path.isdir(CSRC) else []
 
 _lock = threading.Lock()
 _lib = None
 _hooks = None
+_eval = None
 
 
 class TamfBuildError(RuntimeError):
@@ -58,7 +82,15 @@ def _stale() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    """hipcc --offload-arch=gfx950 -shared; cross-compiles without a GPU.  Returns the .so path."""
+    """hipcc --offload-arch=gfx950 -shared; cross-compiles without a GPU.  Returns the .so path.  Builds libtamf_eval.so as well, after
+    the sampler libraries (its own staleness stamp: either side is rebuilt only when ITS sources changed)."""
+    path = build_sampler(force, verbose)
+    build_eval(force, verbose)
+    return path
+
+
+def build_sampler(force: bool = False, verbose: bool = False) -> str:
+    """libtamf_hip.so + libtamf_hip_hooks.so only: what load() / load_hooks() need (they never touch libtamf_eval.so)"""
     if not force and not _stale():
         return LIB_PATH
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -79,14 +111,14 @@ def build(force: bool = False, verbose: bool = False) -> str:
         lock.close()
 
 
-def _compile(hipcc: str, workdir: str, extra, name: str = "libtamf_hip.so"):
+def _compile(hipcc: str, workdir: str, extra, name: str = "libtamf_hip.so", source: str = "tamf_hip.hip"):
     """One hipcc run in `workdir` with -save-temps=obj: the library AND the device assembly of the same compile.
     The product build takes no flags from the environment (tools/ab_build.sh builds the -DTAMF_BENCH / -DTAMF_TIMELINE copies
     for measurements under other file names)."""
     os.makedirs(workdir, exist_ok=True)
     out = os.path.join(workdir, name)
     cmd = [hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-Wno-unused-function", "-save-temps=obj",
-           "-o", out, os.path.join(CSRC, "tamf_hip.hip")] + list(extra)
+           "-o", out, os.path.join(CSRC, source)] + list(extra)
     res = subprocess.run(cmd, capture_output=True, text=True, cwd=workdir)
     if res.returncode != 0:
         raise TamfBuildError("hipcc failed:\n" + res.stdout + res.stderr)
@@ -150,13 +182,98 @@ def _build_locked(hipcc: str, verbose: bool) -> str:
     return LIB_PATH
 
 
+EVAL_STAMP_PATH = EVAL_LIB_PATH + ".src.sha256"
+EVAL_KERNELS = ("_Z23voxelize_lattice_kernel", "_Z26mesh_contains_count_kernel")
+
+
+def eval_source_digest() -> str:
+    """source_digest() of libtamf_eval.so: its translation unit, the headers it includes and the two C headers"""
+    import hashlib
+
+    h = hashlib.sha256()
+    for path in [os.path.join(CSRC, s) for s in EVAL_SOURCES] + [os.path.join(INCLUDE, h_) for h_ in EVAL_HEADERS]:
+        if os.path.exists(path):
+            h.update(os.path.basename(path).encode())
+            with open(path, "rb") as f:
+                h.update(f.read())
+    return h.hexdigest()
+
+
+def _eval_stale() -> bool:
+    if not os.path.exists(EVAL_LIB_PATH):
+        return True
+    try:
+        with open(EVAL_STAMP_PATH) as f:
+            return f.read().strip() != eval_source_digest()
+    except OSError:
+        return True
+
+
+def build_eval(force: bool = False, verbose: bool = False) -> str:
+    """libtamf_eval.so from csrc/tamf_eval.hip, under the same lock and with the same flags as the sampler libraries; the device
+    assembly of the compile goes through _isa_check's scratch report (a spilling score kernel is reported, never fatal)."""
+    if not force and not _eval_stale():
+        return EVAL_LIB_PATH
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        raise TamfBuildError("hipcc not found: cannot build libtamf_eval.so")
+    os.makedirs(os.path.dirname(EVAL_LIB_PATH), exist_ok=True)
+    import fcntl
+    import tempfile
+
+    from . import _isa_check
+
+    lock = open(EVAL_LIB_PATH + ".lock", "w")
+    fcntl.flock(lock, fcntl.LOCK_EX)
+    try:
+        if not force and not _eval_stale():
+            return EVAL_LIB_PATH
+        with tempfile.TemporaryDirectory(prefix="tamf_build_eval_", dir=os.path.dirname(EVAL_LIB_PATH)) as wd:
+            out, asm = _compile(hipcc, wd, [], "libtamf_eval.so", "tamf_eval.hip")
+            if asm is None:
+                raise TamfBuildError("hipcc left no device assembly of libtamf_eval.so to check")
+            rep = _isa_check.scratch_report(asm, prefixes=EVAL_KERNELS)
+            if len(rep) < len(EVAL_KERNELS):
+                raise TamfBuildError(f"libtamf_eval.so: kernel descriptors missing from the device assembly (found {[r[0] for r in rep]})")
+            for name, scratch, vgprs in rep:
+                if verbose:
+                    print(f"libtamf_eval: {name}: {vgprs} vgprs, {scratch} B scratch")
+                if scratch > _isa_check.SCRATCH_LIMIT:
+                    import warnings
+
+                    warnings.warn(f"libtamf_eval: {name} keeps {scratch} bytes of scratch per lane ({vgprs} vgprs)")
+            digest = eval_source_digest()
+            os.replace(out, EVAL_LIB_PATH)
+            with open(EVAL_STAMP_PATH + ".tmp", "w") as f:
+                f.write(digest + "\n")
+            os.replace(EVAL_STAMP_PATH + ".tmp", EVAL_STAMP_PATH)
+    finally:
+        fcntl.flock(lock, fcntl.LOCK_UN)
+        lock.close()
+    if verbose:
+        print("built", EVAL_LIB_PATH)
+    return EVAL_LIB_PATH
+
+
+def load_eval() -> ctypes.CDLL:
+    """libtamf_eval.so (include/tamf_eval.h), built first when missing or stale.  Independent of load(): neither needs the other."""
+    global _eval
+    with _lock:
+        if _eval is None:
+            build_eval()
+            import torch  # noqa: F401  (one HIP runtime per process: torch's, as in load())
+
+            _eval = ctypes.CDLL(EVAL_LIB_PATH)
+        return _eval
+
+
 def load() -> ctypes.CDLL:
     """Load the library (building it first if the in-tree .so is missing or older than its sources).
     Raises - never falls back to a CPU path."""
     global _lib
     with _lock:
         if _lib is None:
-            build()
+            build_sampler()
             # torch ships its own libamdhip64; import it first so that the library binds to the HIP runtime
             # instance torch uses (one runtime per process: shared device memory, streams, contexts).
             import torch  # noqa: F401
@@ -172,7 +289,7 @@ def load_hooks() -> ctypes.CDLL:
     global _hooks
     with _lock:
         if _hooks is None:
-            build()
+            build_sampler()
             import torch  # noqa: F401
 
             _hooks = ctypes.CDLL(HOOKS_PATH)
@@ -201,6 +318,9 @@ EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_pose_decode", "tamf_h2o_dist", "tamf_contact_min_dist", "tamf_mesh_contains", "tamf_transform_points", "tamf_vertex_normals",
     "tamf_power_spectrum_sum",
     "tamf_get_status_flags", "tamf_step_kernel_count", "tamf_loop_stats", "tamf_step_profile", "tamf_refine_profile",
+]
+EVAL_EXPORTS = [  # include/tamf_eval.h: what libtamf_eval.so exports
+    "tamf_eval_last_error", "tamf_voxelize_lattice", "tamf_mesh_contains_count_workspace", "tamf_mesh_contains_count",
 ]
 HOOK_EXPORTS = [  # include/tamf_hip_test.h: additionally in libtamf_hip_hooks.so
     "tamf_test_gemm", "tamf_test_gemm_resid", "tamf_test_attention", "tamf_test_philox", "tamf_test_set_guard_bytes", "tamf_test_check_guards",

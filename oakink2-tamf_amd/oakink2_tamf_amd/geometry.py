@@ -11,6 +11,10 @@ vertex_normals         reference: Meshes(verts, faces).verts_normals_packed() of
                        pytorch3d 0.7.2 _compute_vertex_normals)
 mesh_contains          reference: check_mesh_contains (dev_fn/external/libmesh/inside_mesh.py:8-149 + Cython TriangleHash),
 solid_intersection_volume  the SIV score built on it (script/compute_score/compute_score_siv.py:128-153)
+voxelize_lattice       the same test on an R^3 lattice, per column (libtamf_eval.so): the sign the reference takes from pysdf in
+                       process_sdf (dev_fn/util/sdf_util.py:59-99)
+mesh_contains_count    transf_point_array_np + check_mesh_contains + .sum() of many (hand mesh, transform, point slice) jobs in one
+                       launch (libtamf_eval.so; compute_score_siv.py:136-149)
 All return torch tensors on the inputs' device; no CPU fallback."""
 from __future__ import annotations
 
@@ -205,3 +209,98 @@ def transform_points(obj_traj: torch.Tensor, obj_points: torch.Tensor) -> torch.
         _check(_bind().tamf_transform_points(c_void_p(tr.data_ptr()), c_void_p(pts.data_ptr()), n, T, P, int(dt == torch.float64),
                                              c_void_p(out.data_ptr()), c_void_p(_stream_ptr(dev))))
     return out
+
+
+# ---- libtamf_eval.so (include/tamf_eval.h): the SIV score's context-free kernels -------------------------------------------------
+def _bind_eval():
+    from ctypes import c_char_p, c_int32, c_int64
+
+    from . import _lib
+
+    L = _lib.load_eval()
+    L.tamf_eval_last_error.restype = c_char_p
+    L.tamf_eval_last_error.argtypes = []
+    L.tamf_voxelize_lattice.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                        c_void_p]
+    L.tamf_mesh_contains_count_workspace.restype = c_int64
+    L.tamf_mesh_contains_count_workspace.argtypes = [c_int32, c_int32, c_int32]
+    L.tamf_mesh_contains_count.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p]
+    return L
+
+
+def _check_eval(rc: int, L) -> None:
+    if rc < 0:
+        from .hip_backend import TamfError
+
+        msg = L.tamf_eval_last_error()
+        raise TamfError(f"libtamf_eval error {rc}: {msg.decode() if msg else '?'}")
+
+
+def voxelize_lattice(verts, faces, ticks, resolution: int = 512) -> torch.Tensor:
+    """verts (V,3), faces (F,3) of a closed mesh, ticks (R,3) float64: the tick values of the three axes -> bool (R,R,R), element
+    [i,j,k] = point (ticks[i,0], ticks[j,1], ticks[k,2]) inside the mesh.  Equal to mesh_contains on the R^3 points of
+    np.meshgrid(..., indexing="ij") element for element; the 2D triangle test runs once per lattice column instead of once per point."""
+    import numpy as np
+
+    dev = require_gpu(ticks.device if isinstance(ticks, torch.Tensor) and ticks.is_cuda else None)
+    v_np = verts.detach().cpu().numpy() if isinstance(verts, torch.Tensor) else np.asarray(verts)
+    f_np = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
+    v_np = v_np.astype(np.float64)
+    tri = v_np[f_np].reshape(-1, 3)
+    bmin, bmax = tri.min(axis=0), tri.max(axis=0)
+    scale = np.ascontiguousarray((resolution - 1) / (bmax - bmin), dtype=np.float64)
+    translate = np.ascontiguousarray(0.5 - scale * bmin, dtype=np.float64)
+    v = torch.from_numpy(np.ascontiguousarray(v_np)).to(dev)
+    f = torch.from_numpy(np.ascontiguousarray(f_np.astype(np.int32))).to(dev)
+    tk = torch.as_tensor(ticks).to(device=dev, dtype=torch.float64).contiguous()
+    assert tk.dim() == 2 and tk.shape[1] == 3, "ticks must be (R, 3)"
+    R = int(tk.shape[0])
+    out = torch.empty((R, R, R), device=dev, dtype=torch.uint8)
+    ws = torch.empty(max(1, f.shape[0]) * 16, device=dev, dtype=torch.float64)
+    L = _bind_eval()
+    with torch.cuda.device(dev):
+        _check_eval(L.tamf_voxelize_lattice(c_void_p(v.data_ptr()), c_void_p(f.data_ptr()), int(f.shape[0]), c_void_p(tk.data_ptr()), R,
+                                            scale.ctypes.data_as(c_void_p), translate.ctypes.data_as(c_void_p), int(resolution),
+                                            c_void_p(ws.data_ptr()), c_void_p(out.data_ptr()), c_void_p(_stream_ptr(dev))), L)
+    return out.bool()
+
+
+def mesh_contains_count(hand_verts: torch.Tensor, faces, points: torch.Tensor, pt_off, pt_len, mesh_id, transf,
+                        resolution: int = 512) -> torch.Tensor:
+    """hand_verts (M,V,3) float32 closed meshes sharing faces (F,3); points (P,3) float64 in the object frame; job j counts the points
+    p of points[pt_off[j] : pt_off[j] + pt_len[j]] with R_j p + t_j inside mesh mesh_id[j], transf (J,12) or (J,3,4) float64 = [R | t].
+    -> int64 (J,) on the device.  One launch for all jobs, no host synchronisation; per job the count equals
+    mesh_contains(hand_verts[mesh_id[j]], faces, transformed points).sum()."""
+    import numpy as np
+
+    dev = require_gpu(points.device if points.is_cuda else hand_verts.device)
+    hv = _dev_f32(hand_verts, dev)
+    assert hv.dim() == 3 and hv.shape[2] == 3, "hand_verts must be (M, V, 3)"
+    M, V = int(hv.shape[0]), int(hv.shape[1])
+    f_t = faces if isinstance(faces, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(faces).astype(np.int32)))
+    if not f_t.is_cuda and f_t.numel():  # (device faces are the caller's word; host faces are checked: the kernels index verts by them)
+        assert int(f_t.min()) >= 0 and int(f_t.max()) < V, "face index outside the mesh's vertices"
+    f = f_t.to(device=dev, dtype=torch.int32).contiguous()
+    assert f.dim() == 2 and f.shape[1] == 3, "faces must be (F, 3)"
+    p = points.to(device=dev, dtype=torch.float64).contiguous().reshape(-1, 3)
+    mid = np.ascontiguousarray(np.asarray(mesh_id, dtype=np.int32).reshape(-1))
+    J = int(mid.shape[0])
+    off = np.ascontiguousarray(np.asarray(pt_off, dtype=np.int64).reshape(-1))
+    ln = np.ascontiguousarray(np.asarray(pt_len, dtype=np.int64).reshape(-1))
+    tr = np.ascontiguousarray(np.asarray(transf, dtype=np.float64).reshape(J, 12) if J else np.zeros((0, 12)))
+    assert off.shape[0] == J and ln.shape[0] == J, "one offset, length, mesh id and transform per job"
+    count = torch.empty(J, device=dev, dtype=torch.int64)
+    if J == 0:
+        return count
+    L = _bind_eval()
+    nbytes = int(L.tamf_mesh_contains_count_workspace(M, int(f.shape[0]), J))
+    _check_eval(nbytes, L)
+    ws = torch.empty(nbytes // 8 + 2, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _check_eval(L.tamf_mesh_contains_count(c_void_p(hv.data_ptr()), M, V, c_void_p(f.data_ptr()), int(f.shape[0]),
+                                               c_void_p(p.data_ptr() if p.shape[0] else 0), int(p.shape[0]), J,
+                                               mid.ctypes.data_as(c_void_p), tr.ctypes.data_as(c_void_p), off.ctypes.data_as(c_void_p),
+                                               ln.ctypes.data_as(c_void_p), int(resolution), c_void_p(ws.data_ptr()), nbytes,
+                                               c_void_p(count.data_ptr()), c_void_p(_stream_ptr(dev))), L)
+    return count

@@ -56,9 +56,10 @@ def build_config(a) -> Dict:
     return cfg
 
 
-def load_pairs(cfg) -> List[Tuple[Dict, str]]:
+def load_pairs(cfg, obj_model_loader=None) -> List[Tuple[Dict, str]]:
     """(ground-truth item, path of its save_dict.pkl) of every clip with a save dict, in dataset order, duplicates of `info` skipped
-    (reference compute_score_cr.py:213-231)"""
+    (reference compute_score_cr.py:213-231).  obj_model_loader(obj_id) -> (verts, faces), when given, is handed to the dataset, whose
+    items then carry obj_verts / obj_faces (the SIV score); without it they do not, as before."""
     from ..dataset.interaction_segment import InteractionSegmentData, load_cache_dict
 
     d = cfg["data"]
@@ -67,7 +68,7 @@ def load_pairs(cfg) -> List[Tuple[Dict, str]]:
     dataset = InteractionSegmentData(process_range_list=d.get("process_range"), data_prefix=d.get("data_prefix"),
                                      obj_embedding_prefix=d["obj_embedding_prefix"], enable_obj_model=True,
                                      obj_pointcloud_prefix=d["obj_pointcloud_prefix"], append_reverse_segment=False,
-                                     cache_dict=load_cache_dict(d["cache_dict_filepath"]))
+                                     cache_dict=load_cache_dict(d["cache_dict_filepath"]), obj_model_loader=obj_model_loader)
     root = cfg["debug"]["sample_refine_filepath"]
     seen, pairs = set(), []
     for i in range(len(dataset)):
