@@ -1,6 +1,7 @@
 """Locate / build / load libtamf_hip.so (the C-ABI of include/tamf_hip.h) and, for tests/ and tools/ only, libtamf_hip_hooks.so
 (the same sources with -DTAMF_TEST_HOOKS: + the entry points of include/tamf_hip_test.h); and libtamf_eval.so (include/tamf_eval.h:
-the context-free evaluation kernels of the SIV score), a library of its own with its own sources, stamp and load_eval()."""
+the context-free evaluation kernels of the SIV score), a library of its own with its own sources, stamp and load_eval(); and
+libtamf_mano.so (include/tamf_mano.h: the native MANO hand layer), likewise on its own: build_mano() / load_mano_lib()."""
 from __future__ import annotations
 
 import ctypes
@@ -18,6 +19,9 @@ HEADERS = ("tamf_hip.h", "tamf_hip_test.h")
 EVAL_LIB_PATH = os.path.join(_HERE, "lib", "libtamf_eval.so")
 EVAL_HEADERS = ("tamf_eval.h", "tamf_hip.h")  # (tamf_hip.h for the tamf_status enum)
 EVAL_ONLY = ("tamf_eval.hip", "tamf_voxel.h")  # sources of libtamf_eval.so alone: the sampler libraries neither compile nor stamp them
+MANO_LIB_PATH = os.path.join(_HERE, "lib", "libtamf_mano.so")
+MANO_HEADERS = ("tamf_mano.h", "tamf_hip.h")  # (tamf_hip.h for the tamf_status enum)
+MANO_ONLY = ("tamf_mano.hip", "tamf_mano.h")  # sources of libtamf_mano.so alone
 
 
 def _include_closure(root: str):
@@ -37,12 +41,14 @@ def _include_closure(root: str):
 
 
 EVAL_SOURCES = _include_closure("tamf_eval.hip")  # tamf_eval.hip, tamf_voxel.h and the headers those include (tamf_mesh.h, tamf_device.h)
-SOURCES = [f for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h")) and f not in EVAL_ONLY] if os.path.isdir(CSRC) else []
+MANO_SOURCES = _include_closure("tamf_mano.hip")  # tamf_mano.hip, tamf_mano.h and tamf_device.h
+SOURCES = [f for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h")) and f not in EVAL_ONLY + MANO_ONLY] if os.path.isdir(CSRC) else []
 
 _lock = threading.Lock()
 _lib = None
 _hooks = None
 _eval = None
+_mano = None
 
 
 class TamfBuildError(RuntimeError):
@@ -82,10 +88,12 @@ def _stale() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    """hipcc --offload-arch=gfx950 -shared; cross-compiles without a GPU.  Returns the .so path.  Builds libtamf_eval.so as well, after
-    the sampler libraries (its own staleness stamp: either side is rebuilt only when ITS sources changed)."""
+    """hipcc --offload-arch=gfx950 -shared; cross-compiles without a GPU.  Returns the .so path.  Builds libtamf_eval.so and then
+    libtamf_mano.so as well, after the sampler libraries (each with its own staleness stamp: a library is rebuilt only when ITS
+    sources changed).  One hipcc at a time here, two inside build_sampler()."""
     path = build_sampler(force, verbose)
     build_eval(force, verbose)
+    build_mano(force, verbose)
     return path
 
 
@@ -267,6 +275,92 @@ def load_eval() -> ctypes.CDLL:
         return _eval
 
 
+MANO_STAMP_PATH = MANO_LIB_PATH + ".src.sha256"
+MANO_KERNELS = ("_Z19mano_forward_kernelILi1EE", "_Z19mano_forward_kernelILi2EE", "_Z19mano_forward_kernelILi4EE")
+
+
+def mano_source_digest() -> str:
+    """source_digest() of libtamf_mano.so: its translation unit, the headers it includes and the two C headers.  (csrc/tamf_mano.h and
+    include/tamf_mano.h share a base name: the directory is part of what is hashed.)"""
+    import hashlib
+
+    h = hashlib.sha256()
+    for tag, path in [("csrc/" + s, os.path.join(CSRC, s)) for s in MANO_SOURCES] + [("include/" + h_, os.path.join(INCLUDE, h_)) for h_ in MANO_HEADERS]:
+        if os.path.exists(path):
+            h.update(tag.encode())
+            with open(path, "rb") as f:
+                h.update(f.read())
+    return h.hexdigest()
+
+
+def _mano_stale() -> bool:
+    if not os.path.exists(MANO_LIB_PATH):
+        return True
+    try:
+        with open(MANO_STAMP_PATH) as f:
+            return f.read().strip() != mano_source_digest()
+    except OSError:
+        return True
+
+
+def build_mano(force: bool = False, verbose: bool = False) -> str:
+    """libtamf_mano.so from csrc/tamf_mano.hip: as build_eval() - the same flags, a lock of its own kind, the scratch / VGPR report
+    of its three kernel instantiations (a spilling one is reported, never fatal)."""
+    if not force and not _mano_stale():
+        return MANO_LIB_PATH
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        raise TamfBuildError("hipcc not found: cannot build libtamf_mano.so")
+    os.makedirs(os.path.dirname(MANO_LIB_PATH), exist_ok=True)
+    import fcntl
+    import tempfile
+
+    from . import _isa_check
+
+    lock = open(MANO_LIB_PATH + ".lock", "w")
+    fcntl.flock(lock, fcntl.LOCK_EX)
+    try:
+        if not force and not _mano_stale():
+            return MANO_LIB_PATH
+        with tempfile.TemporaryDirectory(prefix="tamf_build_mano_", dir=os.path.dirname(MANO_LIB_PATH)) as wd:
+            out, asm = _compile(hipcc, wd, [], "libtamf_mano.so", "tamf_mano.hip")
+            if asm is None:
+                raise TamfBuildError("hipcc left no device assembly of libtamf_mano.so to check")
+            rep = _isa_check.scratch_report(asm, prefixes=MANO_KERNELS)
+            if len(rep) < len(MANO_KERNELS):
+                raise TamfBuildError(f"libtamf_mano.so: kernel descriptors missing from the device assembly (found {[r[0] for r in rep]})")
+            for name, scratch, vgprs in rep:
+                if verbose:
+                    print(f"libtamf_mano: {name}: {vgprs} vgprs, {scratch} B scratch")
+                if scratch > _isa_check.SCRATCH_LIMIT:
+                    import warnings
+
+                    warnings.warn(f"libtamf_mano: {name} keeps {scratch} bytes of scratch per lane ({vgprs} vgprs)")
+            digest = mano_source_digest()
+            os.replace(out, MANO_LIB_PATH)
+            with open(MANO_STAMP_PATH + ".tmp", "w") as f:
+                f.write(digest + "\n")
+            os.replace(MANO_STAMP_PATH + ".tmp", MANO_STAMP_PATH)
+    finally:
+        fcntl.flock(lock, fcntl.LOCK_UN)
+        lock.close()
+    if verbose:
+        print("built", MANO_LIB_PATH)
+    return MANO_LIB_PATH
+
+
+def load_mano_lib() -> ctypes.CDLL:
+    """libtamf_mano.so (include/tamf_mano.h), built first when missing or stale.  Independent of load() and load_eval()."""
+    global _mano
+    with _lock:
+        if _mano is None:
+            build_mano()
+            import torch  # noqa: F401  (one HIP runtime per process: torch's, as in load())
+
+            _mano = ctypes.CDLL(MANO_LIB_PATH)
+        return _mano
+
+
 def load() -> ctypes.CDLL:
     """Load the library (building it first if the in-tree .so is missing or older than its sources).
     Raises - never falls back to a CPU path."""
@@ -325,4 +419,7 @@ EVAL_EXPORTS = [  # include/tamf_eval.h: what libtamf_eval.so exports
 HOOK_EXPORTS = [  # include/tamf_hip_test.h: additionally in libtamf_hip_hooks.so
     "tamf_test_gemm", "tamf_test_gemm_resid", "tamf_test_attention", "tamf_test_philox", "tamf_test_set_guard_bytes", "tamf_test_check_guards",
     "tamf_test_poke", "tamf_test_fail_alloc_after", "tamf_bench_gemm", "tamf_bench_attention", "tamf_bench_mfma_rate", "tamf_set_gemm_tuning",
+]
+MANO_EXPORTS = [  # include/tamf_mano.h: what libtamf_mano.so exports
+    "tamf_mano_last_error", "tamf_mano_model_create", "tamf_mano_model_destroy", "tamf_mano_model_set_tiles", "tamf_mano_forward",
 ]

@@ -4,10 +4,11 @@ Only the transformer trunk is on the MI355X path
 (hand side, shape, object), per-frame tokens from [pose | object trajectory | hand->object distance], the same
 8-layer post-LN encoder as G, and the residual output x_in + head(...).  The MANO forward kinematics, vertex normals
 and the brute-force hand->object signed distance that produce `h2o_dist` in the reference (:107-168, external
-manotorch / pytorch3d / chamfer_distance) are "next" rows (section 8f): either the caller supplies
-batch["h2o_dist"] (B, T, 778), or it hands the module its MANO layers (`mano_layer_rh` / `mano_layer_lh`, any callable with
-manotorch's `layer(pose_coeffs=quat (T,16,4), betas=(T,10)) -> .verts (T,778,3), .joints (T,21,3)` contract; the MANO assets
-are licence-gated and not part of this package) and the module runs the reference's whole forward on the GPU: HIP pose decode
+manotorch / pytorch3d / chamfer_distance) run on this package's own kernels too: either the caller supplies
+batch["h2o_dist"] (B, T, 778), or it hands the module its MANO layers (`mano_layer_rh` / `mano_layer_lh`: the native
+`oakink2_tamf_amd.mano.HipManoLayer` built from the user's MANO arrays, or any callable with manotorch's
+`layer(pose_coeffs=quat (T,16,4), betas=(T,10)) -> .verts (T,778,3), .joints (T,21,3)` contract; the MANO assets are
+licence-gated and not part of this package) and the module runs the reference's whole forward on the GPU: HIP pose decode
 -> MANO -> HIP vertex normals -> HIP hand->object distance -> HIP trunk.  The vertex normals (:131-133, pytorch3d's
 verts_normals_packed) are computed when the MANO layer exposes its faces (`th_faces`, as manotorch's does) and returned in
 the result dict like the reference's; they do not enter the distance feature (:165 keeps x2y, unsigned because y_normals
@@ -133,8 +134,8 @@ class SegmentRefineModel(_HipDenoiserBase):
             if hn is not None:
                 res["sample_hand_normals"] = hn
         else:
-            raise KeyError("batch['h2o_dist'] (B, T, 778) must be supplied, or the module built with mano_layer_rh / mano_layer_lh: "
-                           "MANO FK is outside this package (SURVEY.md section 8f, row 1)")
+            raise KeyError("batch['h2o_dist'] (B, T, 778) must be supplied, or the module built with mano_layer_rh / mano_layer_lh "
+                           "(oakink2_tamf_amd.mano.HipManoLayer from the user's MANO arrays, or any layer with manotorch's contract)")
         B, T, _ = x_in.shape
         while True:  # (repeated once in f32 when an activation left the fp16 range of the default f16x3 mode)
             ctx = self._context(B, T)
