@@ -50,6 +50,96 @@ def test_hooks_library_exports_the_test_header_too():
         assert isinstance(getattr(hooks, sym), ctypes._CFuncPtr)
 
 
+def _nm_tamf(path):
+    import subprocess
+
+    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True)
+    assert nm.returncode == 0, nm.stderr
+    return {l.split()[-1] for l in nm.stdout.splitlines() if " T " in l and l.split()[-1].startswith("tamf_")}
+
+
+@pytest.mark.parametrize("lib_i,out_i,file,lists", [(0, 0, "libtamf_hip.so", ["EXPORTS"]), (0, 1, "libtamf_hip_hooks.so", ["EXPORTS", "HOOK_EXPORTS"]),
+                                                    (1, 0, "libtamf_eval.so", ["EVAL_EXPORTS"]), (2, 0, "libtamf_mano.so", ["MANO_EXPORTS"])],
+                         ids=["hip", "hip_hooks", "eval", "mano"])
+def test_every_produced_file_defines_exactly_its_export_list(lib_i, out_i, file, lists):
+    from oakink2_tamf_amd import _lib
+
+    lib = _lib.LIBRARIES[lib_i]
+    want = sum((getattr(_lib, name) for name in lists), [])
+    assert lib.outputs[out_i].file == file and lib.outputs[out_i].exports == want and len(set(want)) == len(want)
+    lib.build()
+    assert _nm_tamf(lib.paths[out_i]) == set(want)
+
+
+def test_library_descriptors():
+    """one description per library (_lib.Library): its own translation unit, sources, stamp and digest; export lists that share no name"""
+    from oakink2_tamf_amd import _lib
+
+    assert _lib.LIBRARIES == (_lib.SAMPLER, _lib.EVAL, _lib.MANO)
+    assert [lib.root for lib in _lib.LIBRARIES] == ["tamf_hip.hip", "tamf_eval.hip", "tamf_mano.hip"]
+    assert [lib.paths for lib in _lib.LIBRARIES] == [[_lib.LIB_PATH, _lib.HOOKS_PATH], [_lib.EVAL_LIB_PATH], [_lib.MANO_LIB_PATH]]
+    assert len(_lib.EXPORTS) == 27 and len(_lib.EVAL_EXPORTS) == 4
+    lists = [_lib.EXPORTS, _lib.HOOK_EXPORTS, _lib.EVAL_EXPORTS, _lib.MANO_EXPORTS]
+    assert len(set().union(*lists)) == sum(len(l) for l in lists)  # pairwise disjoint, no name twice
+    sampler, ev, mano = (lib.sources for lib in _lib.LIBRARIES)
+    assert {"tamf_hip.hip", "tamf_hip_hooks.h", "tamf_geom.h", "tamf_mesh.h"} <= set(sampler)
+    assert not [s for s in sampler if s in ("tamf_eval.hip", "tamf_voxel.h") or s.startswith("tamf_mano")]
+    assert {"tamf_voxel.h", "tamf_mesh.h"} <= set(ev) and "tamf_geom.h" not in ev
+    assert mano == ["tamf_device.h", "tamf_mano.h", "tamf_mano.hip"]
+    assert len({lib.stamp_path for lib in _lib.LIBRARIES}) == 3 and len({lib.digest() for lib in _lib.LIBRARIES}) == 3
+    assert not _lib.EVAL.counted_waits and not _lib.MANO.counted_waits and _lib.SAMPLER.counted_waits
+    assert len(_lib.EVAL.kernels) == 2 and len(_lib.MANO.kernels) == 3
+
+
+def test_hooks_are_compiled_through_one_guard():
+    """csrc/tamf_hip.hip names TAMF_TEST_HOOKS in two conditionals only: the one that selects the launch-lock macro (and the comment
+    above it) and the one that includes csrc/tamf_hip_hooks.h at the end of the file; the hooks themselves are in that header"""
+    from oakink2_tamf_amd import _lib
+
+    lines = open(os.path.join(_lib.CSRC, "tamf_hip.hip")).read().split("\n")
+    hits = [i for i, l in enumerate(lines) if "TAMF_TEST_HOOKS" in l]
+    directives = [i for i in hits if lines[i].lstrip().startswith("#")]
+    assert [lines[i].strip() for i in directives] == ["#ifdef TAMF_TEST_HOOKS"] * 2
+    lock, inc = directives
+    assert lines[lock + 1].startswith("#define TAMF_LAUNCH_LOCK") and lines[lock + 2] == "#else" and lines[lock + 3].startswith("#define TAMF_LAUNCH_LOCK")
+    assert lines[inc + 1:inc + 3] == ['#include "tamf_hip_hooks.h"', "#endif"] and not "".join(lines[inc + 3:]).strip()
+    for i in set(hits) - set(directives):  # the comment block right above the lock-macro conditional
+        assert i < lock and all(l.startswith("//") for l in lines[i:lock])
+    hooks = open(os.path.join(_lib.CSRC, "tamf_hip_hooks.h")).read()
+    assert "TAMF_TEST_HOOKS" not in hooks.replace("-DTAMF_TEST_HOOKS", "")
+    for sym in _lib.HOOK_EXPORTS:
+        assert re.search(r'^extern "C" int %s\(' % sym, hooks, flags=re.M) and not re.search(r'^extern "C" int %s\(' % sym, "\n".join(lines), flags=re.M)
+
+
+@pytest.mark.parametrize("edited,owner", [("csrc/tamf_hip_hooks.h", 0), ("csrc/tamf_voxel.h", 1), ("csrc/tamf_mano.h", 2), ("include/tamf_mano.h", 2)])
+def test_an_edit_makes_only_its_own_library_stale(edited, owner, tmp_path, monkeypatch):
+    """on a copy of csrc/ and include/ with stand-ins for the built files: no compiler runs, the tree is not touched"""
+    import shutil
+
+    from oakink2_tamf_amd import _lib
+
+    for name, src in (("csrc", _lib.CSRC), ("include", _lib.INCLUDE)):
+        shutil.copytree(src, tmp_path / name)
+    monkeypatch.setattr(_lib, "CSRC", str(tmp_path / "csrc"))
+    monkeypatch.setattr(_lib, "INCLUDE", str(tmp_path / "include"))
+    monkeypatch.setattr(_lib, "LIB_DIR", str(tmp_path / "lib"))
+    os.makedirs(_lib.LIB_DIR)
+    assert all(lib.stale() for lib in _lib.LIBRARIES)  # nothing built
+    for lib in _lib.LIBRARIES:
+        for p in lib.paths:
+            assert p.startswith(str(tmp_path))
+            open(p, "w").close()
+        assert lib.stale()  # a library without a stamp is rebuilt
+        with open(lib.stamp_path, "w") as f:
+            f.write(lib.digest() + "\n")
+    assert not any(lib.stale() for lib in _lib.LIBRARIES)
+    with open(tmp_path / edited, "a") as f:
+        f.write("\n// edited\n")
+    assert [lib.stale() for lib in _lib.LIBRARIES] == [i == owner for i in range(3)]
+    os.remove(_lib.SAMPLER.paths[1])  # every produced file has to be there
+    assert _lib.SAMPLER.stale()
+
+
 def test_no_gpu_fails_loudly():
     from oakink2_tamf_amd.hip_backend import TamfContext, TamfError
 

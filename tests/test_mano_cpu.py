@@ -224,10 +224,10 @@ def test_header_exports_and_source_closure():
         hdr = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     assert set(re.findall(r"\b(tamf_[a-z0-9_]+)\s*\(", hdr)) == set(_lib.MANO_EXPORTS) and len(set(_lib.MANO_EXPORTS)) == len(_lib.MANO_EXPORTS)
     assert not set(_lib.MANO_EXPORTS) & set(_lib.EXPORTS + _lib.EVAL_EXPORTS + _lib.HOOK_EXPORTS)
-    assert not [s for s in _lib.SOURCES + _lib.EVAL_SOURCES if s.startswith("tamf_mano")]
-    assert _lib.MANO_SOURCES == ["tamf_device.h", "tamf_mano.h", "tamf_mano.hip"]
-    assert len({_lib.MANO_STAMP_PATH, _lib.STAMP_PATH, _lib.EVAL_STAMP_PATH}) == 3
-    assert len({_lib.mano_source_digest(), _lib.source_digest(), _lib.eval_source_digest()}) == 3
+    assert not [s for s in _lib.SAMPLER.sources + _lib.EVAL.sources if s.startswith("tamf_mano")]
+    assert _lib.MANO.sources == ["tamf_device.h", "tamf_mano.h", "tamf_mano.hip"]
+    assert len({lib.stamp_path for lib in _lib.LIBRARIES}) == 3
+    assert len({lib.digest() for lib in _lib.LIBRARIES}) == 3
     path = _lib.build_mano()
     nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True)
     assert nm.returncode == 0

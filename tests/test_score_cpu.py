@@ -110,7 +110,7 @@ def test_header_and_export_list_name_the_entry_point():
     with open(os.path.join(ROOT, "include", "tamf_hip.h")) as f:
         assert "int tamf_power_spectrum_sum(" in f.read()
     assert "tamf_power_spectrum_sum" in _lib.EXPORTS and len(_lib.EXPORTS) == 27
-    assert "tamf_spectrum.h" in _lib.SOURCES
+    assert "tamf_spectrum.h" in _lib.SAMPLER.sources
 
 
 def test_power_spectrum_sum_rejects_unequal_clips():

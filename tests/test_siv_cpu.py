@@ -88,10 +88,10 @@ def test_eval_header_declares_exactly_the_export_list():
     assert set(re.findall(r"\b(tamf_[a-z0-9_]+)\s*\(", hdr)) == set(_lib.EVAL_EXPORTS) and len(_lib.EVAL_EXPORTS) == 4
     assert len(_lib.EXPORTS) == 27 and not set(_lib.EVAL_EXPORTS) & set(_lib.EXPORTS + _lib.HOOK_EXPORTS)
     # the sampler libraries neither compile nor stamp the score kernels; the score library has its own sources and stamp
-    assert not set(_lib.EVAL_ONLY) & set(_lib.SOURCES) and "tamf_voxel.h" in _lib.EVAL_SOURCES and "tamf_geom.h" in _lib.SOURCES
-    assert "tamf_mesh.h" in _lib.EVAL_SOURCES and "tamf_mesh.h" in _lib.SOURCES and "tamf_geom.h" not in _lib.EVAL_SOURCES  # the include closure
-    assert "tamf_mesh.h" in _lib.EVAL_SOURCES and "tamf_mesh.h" in _lib.SOURCES and "tamf_geom.h" not in _lib.EVAL_SOURCES  # the include closure
-    assert _lib.EVAL_STAMP_PATH != _lib.STAMP_PATH and _lib.eval_source_digest() != _lib.source_digest()
+    sampler, ev = _lib.SAMPLER.sources, _lib.EVAL.sources
+    assert not {"tamf_eval.hip", "tamf_voxel.h"} & set(sampler) and "tamf_voxel.h" in ev and "tamf_geom.h" in sampler
+    assert "tamf_mesh.h" in ev and "tamf_mesh.h" in sampler and "tamf_geom.h" not in ev  # the include closure
+    assert _lib.EVAL.stamp_path != _lib.SAMPLER.stamp_path and _lib.EVAL.digest() != _lib.SAMPLER.digest()
     lib = _lib.load_eval()
     for sym in _lib.EVAL_EXPORTS:
         getattr(lib, sym)
