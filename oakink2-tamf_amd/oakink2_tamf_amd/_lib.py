@@ -6,6 +6,7 @@ that description:
                                  libtamf_hip_hooks.so (-DTAMF_TEST_HOOKS: + csrc/tamf_hip_hooks.h, the entry points of include/tamf_hip_test.h)
   EVAL     csrc/tamf_eval.hip -> libtamf_eval.so (include/tamf_eval.h: the context-free evaluation kernels of the SIV score)
   MANO     csrc/tamf_mano.hip -> libtamf_mano.so (include/tamf_mano.h: the native MANO hand layer)
+  POINTENC csrc/tamf_pointenc.hip -> libtamf_pointenc.so (include/tamf_pointenc.h: the PointBERT point encoder behind obj_embedding)
 Every library has its own sources, stamp and lock: building or loading one never touches another."""
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libtamf_hip.so")
 HOOKS_PATH = os.path.join(LIB_DIR, "libtamf_hip_hooks.so")  # test / measurement build (never loaded by the product path)
 EVAL_LIB_PATH = os.path.join(LIB_DIR, "libtamf_eval.so")
 MANO_LIB_PATH = os.path.join(LIB_DIR, "libtamf_mano.so")
+POINTENC_LIB_PATH = os.path.join(LIB_DIR, "libtamf_pointenc.so")
 
 EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_ctx_create", "tamf_ctx_resize", "tamf_ctx_destroy", "tamf_last_error", "tamf_load_weight", "tamf_finalize_weights",
@@ -43,6 +45,10 @@ EVAL_EXPORTS = [  # include/tamf_eval.h: what libtamf_eval.so exports
 ]
 MANO_EXPORTS = [  # include/tamf_mano.h: what libtamf_mano.so exports
     "tamf_mano_last_error", "tamf_mano_model_create", "tamf_mano_model_destroy", "tamf_mano_model_set_tiles", "tamf_mano_forward",
+]
+POINTENC_EXPORTS = [  # include/tamf_pointenc.h: what libtamf_pointenc.so exports
+    "tamf_pointenc_last_error", "tamf_pointenc_model_create", "tamf_pointenc_load_weight", "tamf_pointenc_finalize", "tamf_pointenc_destroy",
+    "tamf_pointenc_fold_bn", "tamf_pointenc_fps", "tamf_pointenc_group", "tamf_pointenc_workspace_bytes", "tamf_pointenc_encode",
 ]
 
 
@@ -235,12 +241,16 @@ EVAL = Library("libtamf_eval", "tamf_eval.hip", ("tamf_eval.h", "tamf_hip.h"),  
 MANO = Library("libtamf_mano", "tamf_mano.hip", ("tamf_mano.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
                (Output("libtamf_mano.so", (), MANO_EXPORTS),),
                kernels=("_Z19mano_forward_kernelILi1EE", "_Z19mano_forward_kernelILi2EE", "_Z19mano_forward_kernelILi4EE"))
-LIBRARIES = (SAMPLER, EVAL, MANO)
+POINTENC = Library("libtamf_pointenc", "tamf_pointenc.hip", ("tamf_pointenc.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
+                   (Output("libtamf_pointenc.so", (), POINTENC_EXPORTS),),
+                   kernels=("_Z10fps_kernelILi8ELb1EE", "_Z10fps_kernelILi16ELb1EE", "_Z10fps_kernelILi32ELb0EE", "_Z12group_kernel", "_Z11gemm_kernel", "_Z11attn_kernel"))
+LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
+PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Every library, the sampler pair first, each only when ITS sources changed.  One library at a time.  Returns LIB_PATH."""
-    for lib in LIBRARIES:
+    for lib in LIBRARIES + PREPROCESSING:
         lib.build(force, verbose)
     return LIB_PATH
 
@@ -287,6 +297,11 @@ def load_eval() -> ctypes.CDLL:
 def load_mano_lib() -> ctypes.CDLL:
     """libtamf_mano.so (include/tamf_mano.h).  Independent of load() and load_eval()."""
     return _load(MANO, "libtamf_mano.so")
+
+
+def load_pointenc() -> ctypes.CDLL:
+    """libtamf_pointenc.so (include/tamf_pointenc.h).  Independent of the other libraries."""
+    return _load(POINTENC, "libtamf_pointenc.so")
 
 
 def load_from(path: str) -> ctypes.CDLL:

@@ -1,0 +1,182 @@
+"""CPU: the host side of the native point encoder - BatchNorm folding (libtamf_pointenc.so's host entry point), the checkpoint
+prefix mapping, the library's surface, the embed_objects launcher's dry run and cloud preparation, and the embedding file format."""
+import json
+import os
+import re
+import subprocess
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import PKG_PARENT, ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import pointenc_fixture as F  # noqa: E402
+
+
+@pytest.mark.parametrize("case", ["tiny", "mid"])
+def test_bn_folding_matches_the_unfolded_float64_restatement(case):
+    """relu(BN(conv(x))) in float64 from the unfolded parameters against relu(conv'(x)) with the folded float32 weights, evaluated
+    in float64: what is left is the one rounding of each folded weight and bias to float32, <= 2^-24 relative per term, i.e.
+    2^-24 * (sum_i |w'_i x_i| + |b'|) per output"""
+    from oakink2_tamf_amd.model.point_encoder import fold_bn
+
+    cfg = F.CASES[case][0]
+    sd = F.seeded_state_dict(cfg, 11)
+    C = cfg["point_dims"]
+    p = "encoder.first_conv."
+    w, b = fold_bn(sd[p + "0.weight"], sd[p + "0.bias"], sd[p + "1.weight"], sd[p + "1.bias"], sd[p + "1.running_mean"], sd[p + "1.running_var"],
+                   ld_out=(C + 3) // 4 * 4)
+    assert w.shape == (128, (C + 3) // 4 * 4) and w.dtype == np.float32 and not w[:, C:].any()
+    x = np.random.default_rng(0).normal(size=(200, C)).astype(np.float32).astype(np.float64)
+    want = F.pointnet_first_layer(sd, x, torch.float64).numpy()
+    w64, b64 = w[:, :C].astype(np.float64), b.astype(np.float64)
+    got = np.maximum(x @ w64.T + b64, 0.0)
+    bound = 2.0 ** -24 * (np.abs(x) @ np.abs(w64).T + np.abs(b64)) + 1e-15
+    assert (np.abs(got - want) <= bound).all()
+    # the 512 -> 512 layer folds the same way (no padding)
+    p = "encoder.second_conv."
+    w2, b2 = fold_bn(sd[p + "0.weight"], sd[p + "0.bias"], sd[p + "1.weight"], sd[p + "1.bias"], sd[p + "1.running_mean"], sd[p + "1.running_var"])
+    s = sd[p + "1.weight"].astype(np.float64) / np.sqrt(sd[p + "1.running_var"].astype(np.float64) + 1e-5)
+    assert np.array_equal(w2, (s[:, None] * sd[p + "0.weight"][:, :, 0].astype(np.float64)).astype(np.float32))
+    assert np.array_equal(b2, ((sd[p + "0.bias"].astype(np.float64) - sd[p + "1.running_mean"]) * s + sd[p + "1.bias"]).astype(np.float32))
+
+
+def test_bn_folding_rejects_bad_statistics():
+    from oakink2_tamf_amd.model.point_encoder import PointEncoderError, fold_bn
+
+    one = np.ones(4, np.float32)
+    w = np.ones((4, 3), np.float32)
+    with pytest.raises(PointEncoderError, match="running_var"):
+        fold_bn(w, one, one, one, one, -one)
+    bad = one.copy()
+    bad[2] = np.nan
+    with pytest.raises(PointEncoderError, match="channel 2"):
+        fold_bn(w, one, bad, one, one, one)
+
+
+def test_checkpoint_prefix_mapping_reports_missing_and_unexpected_keys():
+    from oakink2_tamf_amd.model.point_encoder import PREFIX, expected_shapes, make_cfg, map_checkpoint
+
+    cfg = make_cfg(F.CASES["tiny"][0])
+    sd = F.seeded_state_dict(cfg, 1)
+    assert {k: v.shape for k, v in sd.items()} == expected_shapes(cfg)
+    ckpt = {PREFIX + k: v for k, v in sd.items()}
+    ckpt[PREFIX + "encoder.first_conv.1.num_batches_tracked"] = np.int64(7)  # a counter, no weight
+    ckpt["module.llm.embed.weight"] = np.zeros(3)                            # another module of the checkpoint: dropped
+    got, missing, unexpected = map_checkpoint(ckpt, cfg)
+    assert set(got) == set(sd) and not missing and not unexpected
+    del ckpt[PREFIX + "norm.bias"], ckpt[PREFIX + "blocks.blocks.0.attn.qkv.weight"]
+    ckpt[PREFIX + "blocks.blocks.0.attn.qkv.bias"] = np.zeros(3)
+    ckpt[PREFIX + "cls_head.0.weight"] = np.zeros(3)
+    got, missing, unexpected = map_checkpoint(ckpt, cfg)
+    assert missing == ["blocks.blocks.0.attn.qkv.weight", "norm.bias"]
+    assert sorted(unexpected) == ["blocks.blocks.0.attn.qkv.bias", "cls_head.0.weight"]
+    assert set(got) == set(sd) - set(missing)
+    # the default configuration is the reference's: 21.9 M parameters, output 768
+    full = expected_shapes(make_cfg())
+    assert 21.8e6 < sum(int(np.prod(s)) for s in full.values()) < 22.0e6 and make_cfg()["trans_dim"] * 2 == 768
+    with pytest.raises(KeyError, match="unknown field"):
+        make_cfg({"transdim": 384})
+
+
+def test_header_exports_and_source_closure():
+    from oakink2_tamf_amd import _lib
+
+    with open(os.path.join(ROOT, "include", "tamf_pointenc.h")) as f:
+        hdr = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    assert set(re.findall(r"\b(tamf_[a-z0-9_]+)\s*\(", hdr)) == set(_lib.POINTENC_EXPORTS) and len(set(_lib.POINTENC_EXPORTS)) == len(_lib.POINTENC_EXPORTS)
+    assert not set(_lib.POINTENC_EXPORTS) & set(_lib.EXPORTS + _lib.EVAL_EXPORTS + _lib.HOOK_EXPORTS + _lib.MANO_EXPORTS)
+    assert _lib.POINTENC.sources == ["tamf_device.h", "tamf_pointenc.h", "tamf_pointenc.hip"]  # no other library's sources
+    assert not [s for lib in _lib.LIBRARIES for s in lib.sources if s.startswith("tamf_pointenc")]
+    assert _lib.POINTENC in _lib.PREPROCESSING and _lib.POINTENC.paths == [_lib.POINTENC_LIB_PATH]
+    assert len({lib.stamp_path for lib in _lib.LIBRARIES + _lib.PREPROCESSING}) == 4
+    path = _lib.POINTENC.build()
+    nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True)
+    assert nm.returncode == 0
+    syms = {ln.split()[-1] for ln in nm.stdout.splitlines() if " T " in ln}
+    assert {s for s in syms if s.startswith("tamf_")} == set(_lib.POINTENC_EXPORTS)
+    lib = _lib.load_pointenc()
+    for s in _lib.POINTENC_EXPORTS:
+        getattr(lib, s)
+
+
+def test_encoder_needs_a_gpu():
+    from oakink2_tamf_amd.hip_backend import TamfError
+    from oakink2_tamf_amd.model.point_encoder import HipPointEncoder
+
+    if torch.cuda.is_available():
+        HipPointEncoder(F.CASES["tiny"][0]).close()
+    else:
+        with pytest.raises(TamfError, match="no CPU fallback"):
+            HipPointEncoder(F.CASES["tiny"][0])
+
+
+def _run(*args):
+    env = dict(os.environ, PYTHONPATH=PKG_PARENT)
+    return subprocess.run([sys.executable, "-m", "oakink2_tamf_amd.launch.embed_objects", *args], capture_output=True, text=True, env=env, timeout=120)
+
+
+def test_embed_objects_dry_run(tmp_path):
+    pc = tmp_path / "pc"
+    pc.mkdir()
+    for oid in ("O02@0015@00001", "C12001"):
+        np.savez(pc / f"{oid}.npz", point=np.zeros((8192, 3), np.float32))
+    r = _run("--data.obj_pointcloud_prefix", str(pc), "--out_dir", str(tmp_path / "emb"), "--dry_run", "--color", "0.5,0.5,0.5", "--seed", "3")
+    assert r.returncode == 0, r.stderr
+    d = json.loads(r.stdout)
+    assert [w["obj_id"] for w in d["work"]] == ["C12001", "O02@0015@00001"] and d["color"] == [0.5, 0.5, 0.5] and d["seed"] == 3 and not d["pc_norm"]
+    assert d["work"][0]["embedding"] == str(tmp_path / "emb" / "C12001.pt") and not (tmp_path / "emb").exists()
+    assert d["cfg"] == dict(point_dims=6, trans_dim=384, depth=12, num_heads=6, num_group=512, group_size=32, encoder_dims=256, npoints=8192)
+    r = _run("--data.obj_pointcloud_prefix", str(pc), "--obj_ids", "C12001", "--dry_run")
+    assert r.returncode == 0 and [w["obj_id"] for w in json.loads(r.stdout)["work"]] == ["C12001"]
+    r = _run("--data.obj_pointcloud_prefix", str(pc), "--obj_ids", "C12001,nope", "--dry_run")
+    assert r.returncode != 0 and "nope.npz not found" in r.stderr
+    # the reference's yaml layout is accepted as --point_encoder.cfg
+    y = tmp_path / "pe.yaml"
+    y.write_text("model : {\n  NAME: PointTransformer,\n  trans_dim: 128,\n  depth: 2,\n  drop_path_rate: 0.1,\n  cls_dim: 40,\n  num_heads: 2,\n"
+                 "  group_size: 8,\n  num_group: 17,\n  encoder_dims: 64,\n  point_dims: 3,\n  use_max_pool: false\n}\nnpoints: 250\n")
+    r = _run("--data.obj_pointcloud_prefix", str(pc), "--point_encoder.cfg", str(y), "--dry_run")
+    assert r.returncode == 0, r.stderr
+    assert json.loads(r.stdout)["cfg"] == dict(F.CASES["tiny"][0], npoints=250)
+    # the shell wrapper
+    r = subprocess.run(["bash", os.path.join(ROOT, "script", "embed_objects.sh"), "-n", "w.pt", "--pc_norm"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "python -m oakink2_tamf_amd.launch.embed_objects --point_encoder.ckpt w.pt --pc_norm" in r.stdout
+    assert subprocess.run(["bash", os.path.join(ROOT, "script", "embed_objects.sh")], capture_output=True, text=True, timeout=60).returncode == 2
+
+
+def test_prepare_cloud():
+    from oakink2_tamf_amd.launch.embed_objects import prepare_cloud
+
+    rng = np.random.default_rng(0)
+    xyz, rgb = rng.normal(size=(50, 3)).astype(np.float32), rng.uniform(size=(50, 3)).astype(np.float32)
+    assert np.array_equal(prepare_cloud(np.concatenate([xyz, rgb], 1), 6, None, False), np.concatenate([xyz, rgb], 1))
+    assert np.array_equal(prepare_cloud(np.concatenate([xyz, rgb], 1), 3, None, False), xyz)
+    p = prepare_cloud(xyz, 6, [0.1, 0.2, 0.3], False)
+    assert p.shape == (50, 6) and np.array_equal(p[:, :3], xyz) and np.allclose(p[:, 3:], [0.1, 0.2, 0.3])
+    with pytest.raises(ValueError, match="--color"):
+        prepare_cloud(xyz, 6, None, False)
+    n = prepare_cloud(np.concatenate([xyz, rgb], 1), 6, None, True)
+    assert np.allclose(n[:, :3].mean(0), 0, atol=1e-6) and abs(np.sqrt((n[:, :3] ** 2).sum(1)).max() - 1) < 1e-6 and np.array_equal(n[:, 3:], rgb)
+    bad = xyz.copy()
+    bad[3, 1] = np.nan
+    with pytest.raises(ValueError, match="non-finite"):
+        prepare_cloud(bad, 3, None, False)
+    with pytest.raises(ValueError, match="expected"):
+        prepare_cloud(np.zeros((5, 4), np.float32), 3, None, False)
+
+
+def test_a_written_embedding_round_trips_through_the_dataset_loader(tmp_path):
+    from oakink2_tamf_amd.dataset.interaction_segment import InteractionSegmentData
+    from oakink2_tamf_amd.launch.embed_objects import save_embedding
+
+    emb = np.random.default_rng(1).normal(size=(1, 768)).astype(np.float32)
+    save_embedding(str(tmp_path / "C12001.pt"), torch.from_numpy(emb)[0])
+    holder = types.SimpleNamespace(interaction_object_list=["C12001"], obj_embedding_prefix=str(tmp_path))
+    store = InteractionSegmentData.load_object_embedding(holder)
+    assert store["C12001"].shape == (768,) and store["C12001"].dtype == np.float32 and np.array_equal(store["C12001"], emb[0])
+    with pytest.raises(ValueError, match="non-finite"):
+        save_embedding(str(tmp_path / "x.pt"), torch.full((768,), float("nan")))
