@@ -2,12 +2,16 @@
 `module.point_encoder.` prefix), point clouds, and a plain-torch restatement of the encoder on given groups (any dtype), written from
 the semantics of reference model/pointbert/point_encoder.py:163-183 and dvae.py:150-221.  Weights are regenerated at test time and
 never stored (the full model has 21.9 M parameters); tools/capture_pointenc_golden.py records their checksum beside the reference's
-outputs, so a fixture and the weights it was captured with cannot drift apart unnoticed."""
+outputs, so a fixture and the weights it was captured with cannot drift apart unnoticed.
+
+SWEEP: configurations at the edges of what tamf_pointenc_model_create accepts, with seeded weights and clouds of their own and the
+float64 / float32 restatement as their reference (tests/test_pointenc_edges_gpu.py).  host_fps / host_knn: include/tamf_pointenc.h's
+selection rules in float32 numpy - the same expression with every product and sum rounded on its own, so they are exact references."""
 from __future__ import annotations
 
 import hashlib
 import math
-from typing import Dict, Mapping
+from typing import Dict, Mapping, Tuple
 
 import numpy as np
 import torch
@@ -19,6 +23,26 @@ CASES = {
     "full": (dict(point_dims=6, trans_dim=384, depth=12, num_heads=6, num_group=512, group_size=32, encoder_dims=256), 8192, 2),
 }
 WEIGHT_SEED = {"tiny": 101, "mid": 102, "full": 103}
+
+
+def _cfg(C, D, depth, G, M, E):
+    return dict(point_dims=C, trans_dim=D, depth=depth, num_heads=D // 64, num_group=G, group_size=M, encoder_dims=E)
+
+
+# case -> (cfg, points per cloud, clouds).  T = num_group + 1 tokens, Tp = round_up(T, 4); the attention kernel's dynamic LDS is
+# 64 * pe_att_ts(T) + 64 bytes, above 64 KiB from T = 993 on.
+SWEEP = {
+    "low": (_cfg(3, 64, 1, 1, 8, 16), 8, 1),          # T = 2 (empty pooling loop), group_size = N, E = 16 (column and K tails)
+    "odd": (_cfg(3, 64, 2, 15, 9, 48), 100, 5),       # T = 16 (one full query panel), tails of 48, group rows of 9, batch of 4 + 1
+    "t24": (_cfg(6, 128, 1, 23, 33, 80), 120, 2),     # Tp = T = 24: the P.V loop has no tail step and no padded column
+    "t23": (_cfg(6, 128, 1, 22, 63, 16), 120, 2),     # Tp - T = 1
+    "wideE": (_cfg(6, 128, 1, 16, 64, 1024), 200, 2),  # T = 17 (a panel with one live row), the widest encoder_dims, group_size 64
+    "wideD": (_cfg(3, 1024, 1, 17, 8, 64), 150, 1),   # trans_dim 1024: 3072 and 4096 columns, 16 heads
+    "g991": (_cfg(3, 64, 1, 991, 8, 16), 1100, 1),    # T = 992: the last below 64 KiB of attention LDS
+    "g992": (_cfg(3, 64, 1, 992, 8, 16), 1100, 1),    # T = 993: the first above
+    "g1024": (_cfg(3, 128, 2, 1024, 8, 16), 1100, 2),  # the upper limit, Tp - T = 3
+}
+SWEEP_SEED = {name: 200 + i for i, name in enumerate(SWEEP)}  # weights: seed, clouds: seed + 100, centres: seed + 200
 
 
 def seeded_state_dict(cfg: Mapping[str, int], seed: int) -> Dict[str, np.ndarray]:
@@ -140,3 +164,60 @@ def restatement(sd: Mapping[str, np.ndarray], cfg: Mapping[str, int], points, ce
         x = x + h @ t(k + "mlp.fc2.weight").T + t(k + "mlp.fc2.bias")
     x = _layer_norm(x, t("norm.weight"), t("norm.bias"))
     return torch.cat([x[:, 0], x[:, 1:].max(1)[0]], -1)
+
+
+def host_fps(xyz: np.ndarray, G: int, start: int) -> Tuple[np.ndarray, float]:
+    """tamf_pointenc_fps on the host for one cloud xyz (N, >= 3) float32: ((dx*dx + dy*dy) + dz*dz) with every product and sum
+    rounded to float32 on its own, the running minimum from 1e10, argmax to the lowest index among equals.  -> (indices (G,) int64,
+    the smallest relative gap between the two largest running minima over the steps; 0 where they are equal, inf for N = 1)"""
+    xyz = np.ascontiguousarray(np.asarray(xyz)[:, :3], dtype=np.float32)
+    N = xyz.shape[0]
+    d, far, idx, gap = np.full(N, np.float32(1e10)), int(start), [], np.inf
+    for _ in range(G):
+        idx.append(far)
+        diff = xyz - xyz[far]
+        d = np.minimum(d, (diff[:, 0] * diff[:, 0] + diff[:, 1] * diff[:, 1]) + diff[:, 2] * diff[:, 2])
+        if N > 1:
+            top = np.partition(d, N - 2)[-2:]
+            gap = min(gap, float((top[1] - top[0]) / top[1]) if top[1] > 0 else 0.0)
+        far = int(np.argmax(d))
+    return np.asarray(idx, dtype=np.int64), gap
+
+
+def host_knn(xyz: np.ndarray, centre_idx, M: int) -> np.ndarray:
+    """tamf_pointenc_group on the host for one cloud: the M nearest points of each centre by the same float32 expression, in
+    ascending (distance, index) order.  xyz (N, >= 3) float32, centre_idx (G,) -> (G, M) int64"""
+    xyz = np.ascontiguousarray(np.asarray(xyz)[:, :3], dtype=np.float32)
+    index = np.arange(xyz.shape[0])
+    out = []
+    for c in np.asarray(centre_idx).reshape(-1):
+        diff = xyz - xyz[int(c)]
+        d = (diff[:, 0] * diff[:, 0] + diff[:, 1] * diff[:, 1]) + diff[:, 2] * diff[:, 2]
+        out.append(np.lexsort((index, d))[:M])
+    return np.asarray(out, dtype=np.int64)
+
+
+def drawn_groups(points: np.ndarray, G: int, M: int, seed: int):
+    """centres drawn without replacement and their host_knn neighbours: points (B, N, C) -> (centre_idx (B, G), nbr_idx (B, G, M))"""
+    rng = np.random.default_rng(seed)
+    centre = np.stack([rng.choice(points.shape[1], G, replace=False) for _ in range(points.shape[0])]).astype(np.int64)
+    return centre, np.stack([host_knn(points[b], centre[b], M) for b in range(points.shape[0])])
+
+
+_SWEEP_CACHE: Dict[str, dict] = {}
+
+
+def sweep_case(name: str) -> dict:
+    """inputs and reference of one SWEEP case, computed once and shared (do not modify): cfg, sd, points, centre_idx, nbr_idx, out64
+    (the float64 restatement) and e32 = max |float32 restatement - float64 restatement|, the unit of the project's 4 * e32 gate"""
+    if name not in _SWEEP_CACHE:
+        cfg, N, B = SWEEP[name]
+        seed = SWEEP_SEED[name]
+        sd = seeded_state_dict(cfg, seed)
+        points = seeded_clouds(B, N, cfg["point_dims"], seed + 100)
+        centre, nbr = drawn_groups(points, cfg["num_group"], cfg["group_size"], seed + 200)
+        out64 = restatement(sd, cfg, points, centre, nbr, torch.float64).numpy()
+        out32 = restatement(sd, cfg, points, centre, nbr, torch.float32).numpy()
+        _SWEEP_CACHE[name] = dict(cfg=cfg, sd=sd, points=points, centre_idx=centre, nbr_idx=nbr, out64=out64,
+                                  e32=float(np.abs(out32.astype(np.float64) - out64).max()))
+    return _SWEEP_CACHE[name]

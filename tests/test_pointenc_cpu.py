@@ -1,5 +1,7 @@
 """CPU: the host side of the native point encoder - BatchNorm folding (libtamf_pointenc.so's host entry point), the checkpoint
-prefix mapping, the library's surface, the embed_objects launcher's dry run and cloud preparation, and the embedding file format."""
+prefix mapping, the library's surface, the embed_objects launcher's dry run and cloud preparation, and the embedding file format;
+and the references of the GPU tests themselves: the plain-torch restatement pinned to the reference's captured outputs, the sweep
+cases of tests/test_pointenc_edges_gpu.py and the host emulations of FPS and grouping."""
 import json
 import os
 import re
@@ -11,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import PKG_PARENT, ROOT
+from conftest import PKG_PARENT, ROOT, load_golden
 
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import pointenc_fixture as F  # noqa: E402
@@ -180,3 +182,74 @@ def test_a_written_embedding_round_trips_through_the_dataset_loader(tmp_path):
     assert store["C12001"].shape == (768,) and store["C12001"].dtype == np.float32 and np.array_equal(store["C12001"], emb[0])
     with pytest.raises(ValueError, match="non-finite"):
         save_embedding(str(tmp_path / "x.pt"), torch.full((768,), float("nan")))
+
+
+@pytest.mark.parametrize("case", ["tiny", "mid", "full"])
+def test_the_float64_restatement_equals_the_captured_reference(case):
+    """tests/pointenc_fixture.restatement is the reference of tests/test_pointenc_edges_gpu.py, so it is held to the reference's own
+    float64 output on the fixture's points and groups.  Gate e32 / 1000 of the fixture: both sides are float64 evaluations of the
+    same sums, whose reordering noise is about 2^-29 of the float32 noise e32, so this leaves six orders of margin and still puts
+    the restatement 4000 x inside the 4 * e32 gate that it carries on the GPU.  Measured: 1.7e-15 (tiny), 2.6e-15 (mid), 2.2e-15
+    (full, 1.3 s) against e32 of 1.0e-6, 1.6e-6, 1.4e-6."""
+    fix = load_golden(f"pointenc_{case}.npz")
+    cfg = F.CASES[case][0]
+    sd = F.seeded_state_dict(cfg, int(fix["weight_seed"]))
+    assert F.state_checksum(sd) == str(fix["state_checksum"]), "the seeded weights are not the ones the fixture was captured with"
+    got = F.restatement(sd, cfg, fix["points"], fix["centre_idx"], fix["nbr_sorted"], dtype=torch.float64).numpy()
+    assert got.shape == fix["out64"].shape and got.dtype == np.float64
+    err, e32 = float(np.abs(got - fix["out64"]).max()), float(fix["e32"])
+    print(f"{case}: max|restatement - reference| = {err:.3e}, e32 = {e32:.3e}")
+    assert e32 > 0 and err <= e32 / 1000
+
+
+@pytest.mark.parametrize("name", list(F.SWEEP))
+def test_every_sweep_case_builds_and_has_a_float32_noise_floor(name):
+    from oakink2_tamf_amd.model.point_encoder import expected_shapes, make_cfg
+
+    cfg, N, B = F.SWEEP[name]
+    c = F.sweep_case(name)
+    G, M = cfg["num_group"], cfg["group_size"]
+    assert {k: v.shape for k, v in c["sd"].items()} == expected_shapes(make_cfg(cfg))
+    assert c["points"].shape == (B, N, cfg["point_dims"]) and c["points"].dtype == np.float32
+    assert c["centre_idx"].shape == (B, G) and c["nbr_idx"].shape == (B, G, M)
+    assert all(len(set(r.tolist())) == G for r in c["centre_idx"]) and np.array_equal(c["nbr_idx"][..., 0], c["centre_idx"])
+    assert all(len(set(g.tolist())) == M for b in c["nbr_idx"] for g in b) and 0 <= c["nbr_idx"].min() and c["nbr_idx"].max() < N
+    assert c["out64"].shape == (B, 2 * cfg["trans_dim"]) and np.isfinite(c["out64"]).all()
+    print(f"{name}: e32 = {c['e32']:.3e}, max|out| = {np.abs(c['out64']).max():.2f}")
+    assert 0 < c["e32"] < 1e-4
+
+
+def test_the_sweep_reaches_the_paths_it_is_there_for():
+    """the properties that make each case worth its run (T = num_group + 1; the attention LDS is 64 * pe_att_ts(T) + 64 bytes)"""
+    def ts(T):
+        return (((T + 3) & ~3) + 31) // 32 * 32 + 4
+
+    T = {k: v[0]["num_group"] + 1 for k, v in F.SWEEP.items()}
+    pad = {k: -t % 4 for k, t in T.items()}
+    assert (T["low"], T["odd"], T["wideE"]) == (2, 16, 17) and F.SWEEP["low"][0]["group_size"] == F.SWEEP["low"][1]
+    assert pad["t24"] == 0 and T["t24"] % 8 == 0 and pad["t23"] == 1 and pad["g1024"] == 3 and {0, 1, 2, 3} <= set(pad.values())
+    assert 64 * ts(T["g991"]) + 64 <= 65536 < 64 * ts(T["g992"]) + 64 and T["g1024"] == 1025
+    assert {16, 48, 80, 1024} <= {v[0]["encoder_dims"] for v in F.SWEEP.values()}
+    assert {9, 33, 63, 64} <= {v[0]["group_size"] for v in F.SWEEP.values()} and F.SWEEP["wideD"][0]["trans_dim"] == 1024
+    from oakink2_tamf_amd.model.point_encoder import MAX_CLOUDS_PER_CALL
+    assert F.SWEEP["odd"][2] == MAX_CLOUDS_PER_CALL + 1
+
+
+def test_host_emulations_of_fps_and_grouping():
+    """host_fps / host_knn against a float64 greedy selection on a cloud without near-ties, and their tie rules on exact ties"""
+    xyz = np.random.default_rng(5).uniform(-1, 1, (300, 3)).astype(np.float32)
+    idx, gap = F.host_fps(xyz, 20, 7)
+    assert gap >= 1e-5 and idx[0] == 7 and len(set(idx.tolist())) == 20
+    x64, d = xyz.astype(np.float64), np.full(300, np.inf)
+    for i in range(19):
+        d = np.minimum(d, ((x64 - x64[idx[i]]) ** 2).sum(-1))
+        assert idx[i + 1] == int(np.argmax(d))
+    nbr = F.host_knn(xyz, idx, 9)
+    d64 = ((x64[None] - x64[idx][:, None]) ** 2).sum(-1)
+    assert np.array_equal(nbr, np.argsort(d64, axis=1, kind="stable")[:, :9]) and np.array_equal(nbr[:, 0], idx)
+    # exact ties: four copies of one point and a mirror pair about the start
+    tie = np.array([[0, 0, 0], [2, 1, 0.5], [0.25, 0, 0], [-2, -1, -0.5], [0, 0, 0], [0, 0, 0], [0, 0, 0]], np.float32)
+    idx, gap = F.host_fps(tie, 7, 0)
+    assert idx.tolist() == [0, 1, 3, 2, 0, 0, 0] and gap == 0.0
+    assert F.host_knn(tie, [4, 1], 5).tolist() == [[0, 4, 5, 6, 2], [1, 2, 0, 4, 5]]
+    assert F.host_fps(tie[:1], 1, 0)[0].tolist() == [0]

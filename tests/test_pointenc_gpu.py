@@ -126,15 +126,9 @@ def test_fps_above_the_register_variants():
     rng = np.random.default_rng(3)
     for N, G in ((20000, 40), (9000, 40)):
         xyz = rng.uniform(-1, 1, (1, N, 3)).astype(np.float32)
-        d, far, want, gap = np.full(N, np.float32(1e10)), N - 1, [], np.inf
-        for i in range(G):
-            want.append(far)
-            diff = xyz[0] - xyz[0, far]
-            d = np.minimum(d, (diff[:, 0] * diff[:, 0] + diff[:, 1] * diff[:, 1]) + diff[:, 2] * diff[:, 2])
-            top = np.sort(d)[-2:]
-            far, gap = int(np.argmax(d)), min(gap, float((top[1] - top[0]) / top[1]))
+        want, gap = F.host_fps(xyz[0], G, N - 1)
         assert gap >= 1e-5
-        assert enc.fps(xyz, num=G, start_index=N - 1).cpu().numpy()[0].tolist() == want
+        assert enc.fps(xyz, num=G, start_index=N - 1).cpu().numpy()[0].tolist() == want.tolist()
 
 
 def test_errors():
