@@ -16,7 +16,7 @@
  *
  * Conventions
  *   - plain C types only; every function returns 0 on success or a negative tamf_status; the message of the
- *     last failure is available from tamf_last_error(ctx) (or tamf_last_error(NULL) for ctx-less failures).
+ *     last failure is available from tamf_last_error(ctx) (tamf_last_error(NULL): the last ctx-less failure of the calling thread, valid until that thread's next one).
  *     Nothing throws across the ABI.
  *   - "dev" pointers are device (HBM) pointers owned by the caller (e.g. torch tensors' data_ptr());
  *     "host" pointers are host memory.  The library owns weights, workspaces and hipGraphs.

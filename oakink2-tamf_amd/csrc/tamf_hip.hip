@@ -42,7 +42,7 @@
 // ------------------------------------------------------------------------------------------------
 // errors
 // ------------------------------------------------------------------------------------------------
-static std::string g_noctx_err;
+static thread_local std::string g_noctx_err;  // context-free failures of the calling thread (tamf_last_error(NULL))
 
 struct OperandBuf {
   void* p = nullptr;
@@ -80,20 +80,40 @@ static constexpr unsigned char GUARD_BYTE = 0xA5;
 static std::atomic<size_t> g_guard_bytes{0};
 static thread_local const char* g_alloc_tag = "";
 
-struct tamf_ctx {
+// Everything dimensioned by (max_batch, max_frames), i.e. what alloc_workspaces / enc_alloc_workspaces fill.  tamf_ctx_resize moves this
+// sub-object out of the context and back as a whole (ws_take / ws_put): a member added here is saved and restored with the rest.
+struct Workspaces {
+  int Bmax = 0, Tmax = 0;
+  long Mmax = 0;
+  float *xs = nullptr, *cobj = nullptr, *X = nullptr, *pstatic = nullptr;
+  OperandBuf xs_op, h1_op, X_op, QK_op, Vt_op, A_op, H_op;
+  // f32: an fp32 operand matrix [rows][ld] is byte for byte the fp32 tensor, so the residual stream X and the sampler state xs ARE
+  // their own operands (X_op.p = X, xs_op.p = xs) and the kernels that used to write both copies write one (X_st / xs_st = null):
+  // 27 MB less per LayerNorm at B = 64 (round 4)
+  void *X_st = nullptr, *xs_st = nullptr;
+  int* tcur = nullptr;
+  unsigned* status = nullptr;  // this context's sticky status word (tamf_device.h): written by its kernels only
+  unsigned char* side_dev = nullptr;
+  int* objnum_dev = nullptr;  // per-clip object counts of tamf_set_cond_ragged
+  // deferred LayerNorm: partial row statistics of the residual stream after the attention / feed-forward sublayer, [Mmax][d / 32]
+  float2 *stat_att = nullptr, *stat_ffn = nullptr;
+  LoopParams* loop_params = nullptr;
+  std::vector<void*> ws_allocs;  // the allocations behind the pointers above
+};
+
+struct tamf_ctx : Workspaces {
   tamf_arch arch{};
-  int prec = 0, device = 0, Bmax = 0, Tmax = 0;
+  int prec = 0, device = 0;
   int d = 0, ff = 0, L = 0, H = 0, hd = 0, P = 0, F = 0, has_t = 0;
   int XK = 0;   // padded K of the fused input GEMM
   int XN = 128; // padded N of the output head
   int EB = 4;  // bytes per logical operand element (f32 4, bf16 2, bf16x3 4 = hi + lo)
   std::string err;
-  std::vector<void*> allocs;     // weights, tables, schedule: live as long as the context
-  std::vector<void*> ws_allocs;  // workspaces dimensioned by (max_batch, max_frames): re-made by tamf_ctx_resize
+  std::vector<void*> allocs;     // weights, tables, schedule: live as long as the context (the workspaces: Workspaces::ws_allocs)
   bool alloc_ws = false;         // dev_alloc files its allocation under ws_allocs
   std::vector<GuardRec> guards;  // guard-band mode (tamf_test_set_guard_bytes): one record per allocation
+  std::map<std::string, std::vector<int64_t>> expected;  // checkpoint key -> shape (expected_shapes), until the weights are finalised
   std::map<std::string, std::vector<float>> raw;
-  std::map<std::string, std::vector<int64_t>> raw_shape;
   bool finalized = false, cond_set = false;
   int n_t = 0;  // rows of the timestep table
   // schedule
@@ -118,25 +138,12 @@ struct tamf_ctx {
   // obj_input_process.poseEmbedding (and the fused bias of input_merge.0)
   float *WtxtT = nullptr, *btxt = nullptr, *WshapeT = nullptr, *bshape = nullptr, *WobjT = nullptr, *bobj = nullptr;
   float *WcT = nullptr, *bc = nullptr, *rh = nullptr, *lh = nullptr;
-  // activations
+  // shape of the conditioning in force (the activations themselves: Workspaces)
   int B = 0, T = 0, S = 0, Sp = 0, Skp = 0, M = 0;
-  long Mmax = 0;
-  float *xs = nullptr, *cobj = nullptr, *X = nullptr, *pstatic = nullptr;
-  OperandBuf xs_op, h1_op, X_op, QK_op, Vt_op, A_op, H_op;
-  // f32: an fp32 operand matrix [rows][ld] is byte for byte the fp32 tensor, so the residual stream X and the sampler state xs ARE
-  // their own operands (X_op.p = X, xs_op.p = xs) and the kernels that used to write both copies write one (X_st / xs_st = null):
-  // 27 MB less per LayerNorm at B = 64 (round 4)
-  void *X_st = nullptr, *xs_st = nullptr;
-  int* tcur = nullptr;
-  unsigned* status = nullptr;  // this context's sticky status word (tamf_device.h): written by its kernels only
-  unsigned char* side_dev = nullptr;
-  int* objnum_dev = nullptr;  // per-clip object counts of tamf_set_cond_ragged
   float* enc_w = nullptr;  // SegmentEncoder (TAMF_KIND_E, tamf_encoder.h): packed weights; its prefix rows live in pstatic [Bmax][3][d]
   int enc_kin = 0;         // ... and the K of its fused input linear map (input_dim + obj_input_dim, padded to 4)
   unsigned host_status = 0;  // status bits raised on the host (TAMF_STATUS_F16_WEIGHT_RANGE at tamf_finalize_weights); never cleared
   std::string weight_note;   // ... and which tensor raised it
-  // deferred LayerNorm: partial row statistics of the residual stream after the attention / feed-forward sublayer, [Mmax][d / 32]
-  float2 *stat_att = nullptr, *stat_ffn = nullptr;
   // graph
   hipStream_t cap_stream = nullptr;
   hipGraph_t graph = nullptr;
@@ -144,7 +151,6 @@ struct tamf_ctx {
   GraphKey graph_key;
   hipEvent_t graph_done = nullptr;  // recorded after the last launch of graph_exec: waited for before it is destroyed
   bool graph_in_flight = false;
-  LoopParams* loop_params = nullptr;
   int sched_cap = 0;  // allocated length of c1 / c2 / sigma
   int graph_captures = 0, graph_launches_last_loop = 0;  // tamf_loop_stats
 #ifdef TAMF_OVERLAP_PROBE
@@ -182,6 +188,23 @@ static int fail(tamf_ctx* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg;
   else g_noctx_err = msg;
   return code;
+}
+// what a context-free entry point returns after its launches
+static int launched() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(nullptr, TAMF_ERR_HIP, hipGetErrorString(e));
+}
+// Kind gating of the entry points: `mask` holds the kinds (KIND_G | ...) that `func` serves.  A null context is TAMF_ERR_INVALID, a
+// context of another kind TAMF_ERR_STATE.
+enum : unsigned { KIND_G = 1u << TAMF_KIND_G, KIND_R = 1u << TAMF_KIND_R, KIND_E = 1u << TAMF_KIND_E };
+static int need_kind(tamf_ctx* ctx, const char* func, unsigned mask) {
+  if (!ctx) return fail(ctx, TAMF_ERR_INVALID, std::string(func) + ": null ctx");
+  if (mask & (1u << ctx->arch.kind)) return 0;
+  if (ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(func) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
+  return fail(ctx, TAMF_ERR_STATE, std::string(func) + (mask == KIND_E   ? " needs a SegmentEncoder (TAMF_KIND_E) context"
+                                                        : mask == KIND_G ? " needs a G context"
+                                                        : mask == KIND_R ? " needs an R context"
+                                                                         : " needs a G or R context"));
 }
 #define HIPCHK(ctx, call)                                                                                         \
   do {                                                                                                            \
@@ -810,49 +833,16 @@ static int enc_alloc_workspaces(tamf_ctx* ctx, int max_batch, int max_frames) {
   ctx->alloc_ws = false;
   return rc;
 }
-static int enc_ctx_create(const tamf_arch* arch, int32_t max_batch, int32_t max_frames, int32_t precision, int32_t device, tamf_ctx** out) {
-  if (precision != TAMF_PREC_F32) return fail(nullptr, TAMF_ERR_INVALID, "SegmentEncoder (TAMF_KIND_E) runs in fp32 only (TAMF_PREC_F32)");
-  if (int rc = enc_check_shape(arch, max_batch, max_frames)) return rc;
-  int ndev = 0;
-  hipError_t de = hipGetDeviceCount(&ndev);
-  if (de != hipSuccess || ndev <= 0)
-    return fail(nullptr, TAMF_ERR_HIP, std::string("no HIP device visible (") + hipGetErrorString(de) + "): libtamf_hip has no CPU fallback");
-  if (device < 0 || device >= ndev) return fail(nullptr, TAMF_ERR_INVALID, "device index out of range");
-  tamf_ctx* ctx = new tamf_ctx();
-  ctx->arch = *arch;
-  ctx->prec = precision;
-  ctx->device = device;
-  ctx->d = arch->latent_dim;
-  ctx->ff = arch->ff_size;
-  ctx->L = arch->num_layers;
-  ctx->H = arch->num_heads;
-  ctx->hd = arch->latent_dim / arch->num_heads;
-  ctx->F = arch->input_dim;
-  ctx->P = ENC_P;
-  ctx->enc_kin = round_up(arch->input_dim + arch->obj_input_dim, 4);
-  auto bail = [&](int rc) {
-    std::string e = ctx->err;
-    tamf_ctx_destroy(ctx);
-    g_noctx_err = e;
-    return rc;
-  };
-  if (hipSetDevice(device) != hipSuccess) return bail(fail(ctx, TAMF_ERR_HIP, "hipSetDevice failed"));
-  hipError_t e = hipFuncSetAttribute((const void*)encoder_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ENC_LDS_BYTES);
-  if (e != hipSuccess) return bail(fail(ctx, TAMF_ERR_HIP, std::string("encoder kernel attribute setup failed: ") + hipGetErrorString(e)));
-  if (int rc = enc_alloc_workspaces(ctx, max_batch, max_frames)) return bail(rc);
-  {
-    std::lock_guard<std::mutex> lk(g_live_mu);
-    g_live_ctx.push_back(ctx);
-  }
-  *out = ctx;
-  return 0;
+static int alloc_workspaces_of_kind(tamf_ctx* ctx, int max_batch, int max_frames) {
+  return ctx->arch.kind == TAMF_KIND_E ? enc_alloc_workspaces(ctx, max_batch, max_frames) : alloc_workspaces(ctx, max_batch, max_frames);
 }
 
-extern "C" int tamf_ctx_create(const tamf_arch* arch, int32_t max_batch, int32_t max_frames, int32_t precision,
-                               int32_t device, tamf_ctx** out) {
-  if (!arch || !out) return fail(nullptr, TAMF_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (arch->kind == TAMF_KIND_E) return enc_ctx_create(arch, max_batch, max_frames, precision, device, out);
+// ---- what tamf_ctx_create does per kind: the checks on the architecture, and the device-side preparation before the workspaces ----
+static int enc_check_create(const tamf_arch* arch, int max_batch, int max_frames, int precision) {
+  if (precision != TAMF_PREC_F32) return fail(nullptr, TAMF_ERR_INVALID, "SegmentEncoder (TAMF_KIND_E) runs in fp32 only (TAMF_PREC_F32)");
+  return enc_check_shape(arch, max_batch, max_frames);
+}
+static int gr_check_arch(const tamf_arch* arch, int precision) {  // (check_dims follows the device checks)
   const int d = arch->latent_dim;
   if (!(d == 128 || d == 256 || d == 512)) return fail(nullptr, TAMF_ERR_INVALID, "latent_dim must be 128, 256 or 512");
   if (arch->num_heads <= 0 || d % arch->num_heads) return fail(nullptr, TAMF_ERR_INVALID, "bad num_heads");
@@ -863,31 +853,68 @@ extern "C" int tamf_ctx_create(const tamf_arch* arch, int32_t max_batch, int32_t
   if (arch->input_dim <= 0 || arch->input_dim > 128) return fail(nullptr, TAMF_ERR_INVALID, "input_dim must be in [1,128]");
   if (precision < 0 || precision > TAMF_PREC_F16X3) return fail(nullptr, TAMF_ERR_INVALID, "unknown precision");
   if (arch->kind != TAMF_KIND_G && arch->kind != TAMF_KIND_R) return fail(nullptr, TAMF_ERR_INVALID, "unknown model kind");
+  return 0;
+}
+static int enc_prepare(tamf_ctx* ctx) {
+  hipError_t e = hipFuncSetAttribute((const void*)encoder_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ENC_LDS_BYTES);
+  if (e != hipSuccess) return fail(ctx, TAMF_ERR_HIP, std::string("encoder kernel attribute setup failed: ") + hipGetErrorString(e));
+  return 0;
+}
+static int gr_prepare(tamf_ctx* ctx) {  // workgroup slots of the device, kernel attributes, the capture stream
+  {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && cus > 0)
+      g_wg_slots_dev[ctx->device & 63].store(2 * cus, std::memory_order_relaxed);
+  }
+  hipError_t pe;
+  {
+    TAMF_STATE_LOCK;  // (one context at a time sets the kernel attributes of a device: they are idempotent, this only avoids the duplicate work)
+    pe = prepare_all<OpF32>();
+    if (pe == hipSuccess && ctx->prec != TAMF_PREC_F32) TAMF_WITH_OP(ctx->prec, pe = prepare_all<Op>());
+  }
+  if (pe != hipSuccess) return fail(ctx, TAMF_ERR_HIP, std::string("kernel attribute setup failed: ") + hipGetErrorString(pe));
+  if (hipStreamCreateWithFlags(&ctx->cap_stream, hipStreamNonBlocking) != hipSuccess) return fail(ctx, TAMF_ERR_HIP, "hipStreamCreate failed");
+  return 0;
+}
+
+static std::map<std::string, std::vector<int64_t>> expected_shapes(const tamf_ctx* c);
+
+extern "C" int tamf_ctx_create(const tamf_arch* arch, int32_t max_batch, int32_t max_frames, int32_t precision,
+                               int32_t device, tamf_ctx** out) {
+  if (!arch || !out) return fail(nullptr, TAMF_ERR_INVALID, "null argument");
+  *out = nullptr;
+  const bool enc = arch->kind == TAMF_KIND_E;
+  if (int rc = enc ? enc_check_create(arch, max_batch, max_frames, precision) : gr_check_arch(arch, precision)) return rc;
   int ndev = 0;
   hipError_t de = hipGetDeviceCount(&ndev);
   if (de != hipSuccess || ndev <= 0)
     return fail(nullptr, TAMF_ERR_HIP, std::string("no HIP device visible (") + hipGetErrorString(de) +
                                            "): libtamf_hip has no CPU fallback");
   if (device < 0 || device >= ndev) return fail(nullptr, TAMF_ERR_INVALID, "device index out of range");
+  if (!enc)
+    if (int rc = check_dims(arch, max_batch, max_frames)) return rc;
 
-  if (int rc = check_dims(arch, max_batch, max_frames)) return rc;
   tamf_ctx* ctx = new tamf_ctx();
   ctx->arch = *arch;
   ctx->prec = precision;
   ctx->device = device;
-  ctx->Bmax = max_batch;
-  ctx->Tmax = max_frames;
-  ctx->d = d;
+  ctx->d = arch->latent_dim;
   ctx->ff = arch->ff_size;
   ctx->L = arch->num_layers;
   ctx->H = arch->num_heads;
-  ctx->hd = hd;
+  ctx->hd = arch->latent_dim / arch->num_heads;
   ctx->F = arch->input_dim;
   ctx->has_t = arch->kind == TAMF_KIND_G ? 1 : 0;
-  ctx->P = arch->kind == TAMF_KIND_G ? 5 : 3;
-  ctx->XK = arch->kind == TAMF_KIND_G ? 128 : round_up(arch->input_dim + arch->h2o_dim, 64);
   ctx->EB = precision == TAMF_PREC_BF16 ? 2 : 4;
-  ctx->layers.resize(ctx->L);
+  if (enc) {
+    ctx->P = ENC_P;
+    ctx->enc_kin = round_up(arch->input_dim + arch->obj_input_dim, 4);
+  } else {
+    ctx->P = arch->kind == TAMF_KIND_G ? 5 : 3;
+    ctx->XK = arch->kind == TAMF_KIND_G ? 128 : round_up(arch->input_dim + arch->h2o_dim, 64);
+    ctx->layers.resize(ctx->L);
+  }
+  ctx->expected = expected_shapes(ctx);
 
   auto bail = [&](int rc) {
     std::string e = ctx->err;
@@ -896,24 +923,9 @@ extern "C" int tamf_ctx_create(const tamf_arch* arch, int32_t max_batch, int32_t
     return rc;
   };
   if (hipSetDevice(device) != hipSuccess) return bail(fail(ctx, TAMF_ERR_HIP, "hipSetDevice failed"));
-  {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
-      g_wg_slots_dev[device & 63].store(2 * cus, std::memory_order_relaxed);
-  }
-  hipError_t pe;
-  {
-    TAMF_STATE_LOCK;  // (one context at a time sets the kernel attributes of a device: they are idempotent, this only avoids the duplicate work)
-    pe = prepare_all<OpF32>();
-    if (pe == hipSuccess && precision != TAMF_PREC_F32) TAMF_WITH_OP(precision, pe = prepare_all<Op>());
-  }
-  if (pe != hipSuccess)
-    return bail(fail(ctx, TAMF_ERR_HIP, std::string("kernel attribute setup failed: ") + hipGetErrorString(pe)));
-  if (hipStreamCreateWithFlags(&ctx->cap_stream, hipStreamNonBlocking) != hipSuccess)
-    return bail(fail(ctx, TAMF_ERR_HIP, "hipStreamCreate failed"));
-
-  if (int rc = alloc_workspaces(ctx, max_batch, max_frames)) return bail(rc);
-  if (hipEventCreateWithFlags(&ctx->graph_done, hipEventDisableTiming) != hipSuccess)
+  if (int rc = enc ? enc_prepare(ctx) : gr_prepare(ctx)) return bail(rc);
+  if (int rc = alloc_workspaces_of_kind(ctx, max_batch, max_frames)) return bail(rc);
+  if (!enc && hipEventCreateWithFlags(&ctx->graph_done, hipEventDisableTiming) != hipSuccess)
     return bail(fail(ctx, TAMF_ERR_HIP, "hipEventCreate failed"));
   {
     std::lock_guard<std::mutex> lk(g_live_mu);
@@ -946,149 +958,84 @@ extern "C" void tamf_ctx_destroy(tamf_ctx* ctx) {
 
 static int retire_graph(tamf_ctx* ctx);
 
-// the members alloc_workspaces() fills: saved / restored as a unit by tamf_ctx_resize
-struct WorkspaceSet {
-  float *xs, *cobj, *X, *pstatic;
-  OperandBuf xs_op, h1_op, X_op, QK_op, Vt_op, A_op, H_op;
-  void *X_st, *xs_st;
-  int* tcur;
-  unsigned* status;
-  unsigned char* side_dev;
-  int* objnum_dev;
-  float2 *stat_att, *stat_ffn;
-  LoopParams* loop_params;
-  long Mmax;
-  int Bmax, Tmax;
-  std::vector<void*> ws_allocs;
-  std::vector<GuardRec> ws_guards;
+// a context's workspace set, moved out of it (ws_take): the sub-object and the guard records of its allocations
+struct TakenWorkspaces {
+  Workspaces ws;
+  std::vector<GuardRec> guards;
 };
-static WorkspaceSet ws_take(tamf_ctx* c) {  // moves the workspace set out of the context (its lists of workspace allocations / guards become empty)
-  WorkspaceSet w{c->xs, c->cobj, c->X, c->pstatic, c->xs_op, c->h1_op, c->X_op, c->QK_op, c->Vt_op, c->A_op, c->H_op, c->X_st, c->xs_st, c->tcur,
-                 c->status, c->side_dev, c->objnum_dev, c->stat_att, c->stat_ffn, c->loop_params, c->Mmax, c->Bmax, c->Tmax, {}, {}};
-  w.ws_allocs.swap(c->ws_allocs);
-  for (const GuardRec& g : c->guards)
-    if (g.ws) w.ws_guards.push_back(g);
-  c->guards.erase(std::remove_if(c->guards.begin(), c->guards.end(), [](const GuardRec& g) { return g.ws; }), c->guards.end());
-  return w;
+static TakenWorkspaces ws_take(tamf_ctx* c) {  // (the context is left with no workspaces: null pointers, empty lists)
+  TakenWorkspaces t;
+  std::swap(t.ws, static_cast<Workspaces&>(*c));
+  const auto first_ws = std::stable_partition(c->guards.begin(), c->guards.end(), [](const GuardRec& g) { return !g.ws; });
+  t.guards.assign(first_ws, c->guards.end());
+  c->guards.erase(first_ws, c->guards.end());
+  return t;
 }
-static void ws_put(tamf_ctx* c, WorkspaceSet& w) {
-  c->xs = w.xs; c->cobj = w.cobj; c->X = w.X; c->pstatic = w.pstatic;
-  c->xs_op = w.xs_op; c->h1_op = w.h1_op; c->X_op = w.X_op; c->QK_op = w.QK_op; c->Vt_op = w.Vt_op; c->A_op = w.A_op; c->H_op = w.H_op;
-  c->X_st = w.X_st; c->xs_st = w.xs_st; c->tcur = w.tcur; c->status = w.status; c->side_dev = w.side_dev; c->objnum_dev = w.objnum_dev;
-  c->stat_att = w.stat_att; c->stat_ffn = w.stat_ffn; c->loop_params = w.loop_params;
-  c->Mmax = w.Mmax; c->Bmax = w.Bmax; c->Tmax = w.Tmax;
-  c->ws_allocs.swap(w.ws_allocs);
-  c->guards.insert(c->guards.end(), w.ws_guards.begin(), w.ws_guards.end());
+static void ws_put(tamf_ctx* c, TakenWorkspaces& t) {  // (into a context without workspaces; their guard records go to the end of the list)
+  std::swap(t.ws, static_cast<Workspaces&>(*c));
+  c->guards.insert(c->guards.end(), t.guards.begin(), t.guards.end());
+}
+static void ws_free(const TakenWorkspaces& t) {
+  for (void* p : t.ws.ws_allocs) (void)hipFree(p);
 }
 
 // Transactional: the new workspaces are allocated FIRST, beside the old ones; only when every allocation has succeeded
 // are the old ones freed.  On failure (the likely one: a larger batch that does not fit) the partial new set is freed, the old set -
 // pointers, dimensions, conditioning - is put back and the context keeps working at its old size; the captured graph is gone either
 // way (it holds the old pointers' kernels: harmless, but it is re-captured on the next loop).  The sticky status word travels with
-// the context: bits raised and not yet read survive the resize.
+// the context: bits raised and not yet read survive the resize.  A SegmentEncoder context has no graph, conditioning or status word:
+// only its prefix rows and object counts are dimensioned.
 extern "C" int tamf_ctx_resize(tamf_ctx* ctx, int32_t max_batch, int32_t max_frames) {
   TAMF_LAUNCH_LOCK;
   if (!ctx) return fail(ctx, TAMF_ERR_INVALID, "null ctx");
-  if (ctx->arch.kind == TAMF_KIND_E) {  // (no graph, no conditioning: only the prefix rows and object counts are dimensioned)
-    if (int rc = enc_check_shape(&ctx->arch, max_batch, max_frames)) {
-      ctx->err = g_noctx_err;
-      return rc;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, hipDeviceSynchronize());
-    WorkspaceSet old = ws_take(ctx);
-    if (int rc = enc_alloc_workspaces(ctx, max_batch, max_frames)) {
-      WorkspaceSet part = ws_take(ctx);
-      for (void* p : part.ws_allocs) (void)hipFree(p);
-      ws_put(ctx, old);
-      return rc;
-    }
-    for (void* p : old.ws_allocs) (void)hipFree(p);
-    return 0;
-  }
-  if (int rc = check_dims(&ctx->arch, max_batch, max_frames)) {
+  const bool enc = ctx->arch.kind == TAMF_KIND_E;
+  if (int rc = enc ? enc_check_shape(&ctx->arch, max_batch, max_frames) : check_dims(&ctx->arch, max_batch, max_frames)) {
     ctx->err = g_noctx_err;
     return rc;
   }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipDeviceSynchronize());
-  TRY(retire_graph(ctx));
-  if (ctx->graph) { (void)hipGraphDestroy(ctx->graph); ctx->graph = nullptr; }
-  ctx->graph_key = GraphKey{};
-  WorkspaceSet old = ws_take(ctx);
-  int rc = alloc_workspaces(ctx, max_batch, max_frames);
-  if (rc == 0 && old.status && ctx->status &&
-      hipMemcpy(ctx->status, old.status, 16, hipMemcpyDeviceToDevice) != hipSuccess)
+  if (!enc) TRY(retire_graph(ctx));
+  TakenWorkspaces old = ws_take(ctx);
+  int rc = alloc_workspaces_of_kind(ctx, max_batch, max_frames);
+  if (rc == 0 && old.ws.status && ctx->status &&
+      hipMemcpy(ctx->status, old.ws.status, 16, hipMemcpyDeviceToDevice) != hipSuccess)
     rc = fail(ctx, TAMF_ERR_HIP, "tamf_ctx_resize: carrying the status word over failed");
   if (rc != 0) {
     const std::string why = ctx->err;
-    WorkspaceSet part = ws_take(ctx);  // whatever alloc_workspaces got before it failed
-    for (void* p : part.ws_allocs) (void)hipFree(p);
+    ws_free(ws_take(ctx));  // whatever the allocator got before it failed
     ws_put(ctx, old);
-    ctx->alloc_ws = false;
     ctx->err = "tamf_ctx_resize(" + std::to_string(max_batch) + ", " + std::to_string(max_frames) + ") failed, the context keeps its " +
                std::to_string(ctx->Bmax) + " x " + std::to_string(ctx->Tmax) + " workspaces: " + why;
     return rc;
   }
-  for (void* p : old.ws_allocs) (void)hipFree(p);
-  ctx->cond_set = false;
-  ctx->B = ctx->T = ctx->S = ctx->Sp = ctx->Skp = ctx->M = 0;
+  ws_free(old);
+  if (!enc) {
+    ctx->cond_set = false;
+    ctx->B = ctx->T = ctx->S = ctx->Sp = ctx->Skp = ctx->M = 0;
+  }
   return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
 // weights
 // ------------------------------------------------------------------------------------------------
+// the state-dict key set of the context's kind (SegmentEncoder: segment_encoder.py:16-75) with the shape of every tensor
 static std::map<std::string, std::vector<int64_t>> expected_shapes(const tamf_ctx* c) {
   std::map<std::string, std::vector<int64_t>> m;
   const int64_t d = c->d, ff = c->ff;
+  const int kind = c->arch.kind;
   auto lin = [&](const std::string& n, int64_t o, int64_t i) {
     m[n + ".weight"] = {o, i};
     m[n + ".bias"] = {o};
   };
-  if (c->arch.kind == TAMF_KIND_E) {  // SegmentEncoder (segment_encoder.py:16-75): its state-dict key set
-    m["hand_side_process.rh_embed"] = {d};
-    m["hand_side_process.lh_embed"] = {d};
-    lin("hand_shape_process.shape_embed", d, c->arch.hand_shape_dim);
-    lin("obj_embed_process.embedding", d, c->arch.obj_embed_dim);
-    m["classification_token"] = {1, 1, d};
-    lin("input_process.poseEmbedding", d, c->arch.input_dim);
-    lin("obj_input_process.poseEmbedding", d, c->arch.obj_input_dim);
-    lin("input_merge.0", d, 2 * d);
-    lin("input_merge.2", d, d);
-    m["sequence_pos_encoder.pe"] = {5000, 1, d};
-    for (int l = 0; l < c->L; ++l) {
-      const std::string p = "seqTransEncoder.layers." + std::to_string(l);
-      m[p + ".self_attn.in_proj_weight"] = {3 * d, d};
-      m[p + ".self_attn.in_proj_bias"] = {3 * d};
-      lin(p + ".self_attn.out_proj", d, d);
-      lin(p + ".linear1", ff, d);
-      lin(p + ".linear2", d, ff);
-      m[p + ".norm1.weight"] = {d};
-      m[p + ".norm1.bias"] = {d};
-      m[p + ".norm2.weight"] = {d};
-      m[p + ".norm2.bias"] = {d};
-    }
-    lin("output_process.poseFinal.0", d, d);
-    lin("output_process.poseFinal.2", d, d);
-    lin("output_process.poseFinal.4", c->arch.input_dim, d);
-    return m;
-  }
   m["hand_side_process.rh_embed"] = {d};
   m["hand_side_process.lh_embed"] = {d};
   lin("hand_shape_process.shape_embed", d, c->arch.hand_shape_dim);
   lin("obj_embed_process.embedding", d, c->arch.obj_embed_dim);
   lin("input_process.poseEmbedding", d, c->arch.input_dim);
   lin("obj_input_process.poseEmbedding", d, c->arch.obj_input_dim);
-  if (c->arch.kind == TAMF_KIND_R) {
-    lin("h2o_dist_input_process.poseEmbedding", d, c->arch.h2o_dim);
-    lin("input_merge.0", d, 3 * d);
-  } else {
-    lin("input_merge.0", d, 2 * d);
-    lin("embed_timestep.time_embed.0", d, d);
-    lin("embed_timestep.time_embed.2", d, d);
-    lin("embed_text", d, c->arch.clip_dim);
-  }
+  lin("input_merge.0", d, (kind == TAMF_KIND_R ? 3 : 2) * d);
   lin("input_merge.2", d, d);
   m["sequence_pos_encoder.pe"] = {5000, 1, d};
   for (int l = 0; l < c->L; ++l) {
@@ -1103,6 +1050,20 @@ static std::map<std::string, std::vector<int64_t>> expected_shapes(const tamf_ct
     m[p + ".norm2.weight"] = {d};
     m[p + ".norm2.bias"] = {d};
   }
+  if (kind == TAMF_KIND_E) {
+    m["classification_token"] = {1, 1, d};
+    lin("output_process.poseFinal.0", d, d);
+    lin("output_process.poseFinal.2", d, d);
+    lin("output_process.poseFinal.4", c->arch.input_dim, d);
+    return m;
+  }
+  if (kind == TAMF_KIND_R) {
+    lin("h2o_dist_input_process.poseEmbedding", d, c->arch.h2o_dim);
+  } else {
+    lin("embed_timestep.time_embed.0", d, d);
+    lin("embed_timestep.time_embed.2", d, d);
+    lin("embed_text", d, c->arch.clip_dim);
+  }
   lin("output_process.poseFinal", c->arch.input_dim, d);
   return m;
 }
@@ -1111,24 +1072,47 @@ extern "C" int tamf_load_weight(tamf_ctx* ctx, const char* name, const float* ho
                                 int32_t ndim) {
   if (!ctx || !name || !host_data || !shape || ndim <= 0) return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
   if (ctx->finalized) return fail(ctx, TAMF_ERR_STATE, "weights already finalised");
-  const auto exp = expected_shapes(ctx);
-  const auto it = exp.find(name);
-  if (it == exp.end()) return 0;  // strict=False: unexpected keys are ignored (e.g. clip_model.*, aliased pe buffer)
+  const auto it = ctx->expected.find(name);
+  if (it == ctx->expected.end()) return 0;  // strict=False: unexpected keys are ignored (e.g. clip_model.*, aliased pe buffer)
   std::vector<int64_t> shp(shape, shape + ndim);
   if (shp != it->second) return fail(ctx, TAMF_ERR_INVALID, std::string("shape mismatch for ") + name);
   int64_t n = 1;
   for (auto v : shp) n *= v;
   ctx->raw[name].assign(host_data, host_data + n);
-  ctx->raw_shape[name] = shp;
   return 0;
 }
-
-template <class Op>
-static OperandBuf ob_cast(const OperandBuf& o) { return o; }
 
 static int upload_f32(tamf_ctx* ctx, const std::string& name, float** p) {
   const auto& v = ctx->raw.at(name);
   return dev_upload(ctx, p, v.data(), v.size());
+}
+static int upload_T(tamf_ctx* ctx, const std::string& name, int N, int K, float** p) {  // W [N][K] -> W^T [K][N] (prefix_rows_kernel)
+  const float* W = ctx->raw.at(name).data();
+  std::vector<float> t((size_t)N * K);
+  for (int n = 0; n < N; ++n)
+    for (int k = 0; k < K; ++k) t[(size_t)k * N + n] = W[(size_t)n * K + k];
+  return dev_upload(ctx, p, t.data(), t.size());
+}
+// the tables of the prefix rows that every kind has (prefix_rows_kernel): hand shape, object embedding, hand side
+static int upload_prefix_tables(tamf_ctx* ctx) {
+  const int d = ctx->d;
+  TRY(upload_T(ctx, "hand_shape_process.shape_embed.weight", d, ctx->arch.hand_shape_dim, &ctx->WshapeT));
+  TRY(upload_f32(ctx, "hand_shape_process.shape_embed.bias", &ctx->bshape));
+  TRY(upload_T(ctx, "obj_embed_process.embedding.weight", d, ctx->arch.obj_embed_dim, &ctx->WobjT));
+  TRY(upload_f32(ctx, "obj_embed_process.embedding.bias", &ctx->bobj));
+  TRY(upload_f32(ctx, "hand_side_process.rh_embed", &ctx->rh));
+  return upload_f32(ctx, "hand_side_process.lh_embed", &ctx->lh);
+}
+// One block of the composed input map, in float64: out[n * ld_n + k * ld_k] = sum_j W_m1[n][col0 + j] W_x[j][k] (n, j < d; k < K), where
+// W_m1 = input_merge.0.weight [d][mk] and W_x [d][K] is the embedding that feeds its columns col0 .. col0 + d.  ld_k = 1: row-major
+// rows of the fused weight; ld_n = 1: transposed (WcT of cobj_kernel).
+static void compose_block(const float* Wm1, int mk, int col0, int d, const float* Wx, int K, float* out, long ld_n, long ld_k) {
+  for (int n = 0; n < d; ++n)
+    for (int k = 0; k < K; ++k) {
+      double a = 0;
+      for (int j = 0; j < d; ++j) a += (double)Wm1[(size_t)n * mk + col0 + j] * Wx[(size_t)j * K + k];
+      out[n * ld_n + k * ld_k] = (float)a;
+    }
 }
 
 // SegmentEncoder weights -> the packed layout of tamf_encoder.h (EncHeadOff, then one EncLayerOff block per layer) + the prefix-row
@@ -1149,17 +1133,9 @@ static int enc_finalize(tamf_ctx* ctx) {
       double acc_b = bm1[n];
       for (int j = 0; j < d; ++j) acc_b += (double)Wm1[(size_t)n * 2 * d + j] * bp[j] + (double)Wm1[(size_t)n * 2 * d + d + j] * bq[j];
       w[ho.bin + n] = (float)acc_b;
-      for (int k = 0; k < F; ++k) {
-        double a = 0;
-        for (int j = 0; j < d; ++j) a += (double)Wm1[(size_t)n * 2 * d + j] * Wp[(size_t)j * F + k];
-        w[ho.win + (long)n * kin + k] = (float)a;
-      }
-      for (int k = 0; k < qd; ++k) {
-        double a = 0;
-        for (int j = 0; j < d; ++j) a += (double)Wm1[(size_t)n * 2 * d + d + j] * Wq[(size_t)j * qd + k];
-        w[ho.win + (long)n * kin + F + k] = (float)a;
-      }
     }
+    compose_block(Wm1, 2 * d, 0, d, Wp, F, w.data() + ho.win, kin, 1);
+    compose_block(Wm1, 2 * d, d, d, Wq, qd, w.data() + ho.win + F, kin, 1);
   }
   put(ho.wm2, "input_merge.2.weight", (size_t)d * d);
   put(ho.bm2, "input_merge.2.bias", d);
@@ -1193,20 +1169,7 @@ static int enc_finalize(tamf_ctx* ctx) {
   }
   TRY(dev_upload(ctx, &ctx->enc_w, w.data(), w.size()));
   TRY(upload_f32(ctx, "sequence_pos_encoder.pe", &ctx->pe));
-  auto upload_T = [&](const std::string& name, int N, int K, float** p) -> int {  // W [N][K] -> W^T [K][N] (prefix_rows_kernel)
-    const float* W = R(name);
-    std::vector<float> t((size_t)N * K);
-    for (int n = 0; n < N; ++n)
-      for (int k = 0; k < K; ++k) t[(size_t)k * N + n] = W[(size_t)n * K + k];
-    return dev_upload(ctx, p, t.data(), t.size());
-  };
-  TRY(upload_T("hand_shape_process.shape_embed.weight", d, ctx->arch.hand_shape_dim, &ctx->WshapeT));
-  TRY(upload_f32(ctx, "hand_shape_process.shape_embed.bias", &ctx->bshape));
-  TRY(upload_T("obj_embed_process.embedding.weight", d, ctx->arch.obj_embed_dim, &ctx->WobjT));
-  TRY(upload_f32(ctx, "obj_embed_process.embedding.bias", &ctx->bobj));
-  TRY(upload_f32(ctx, "hand_side_process.rh_embed", &ctx->rh));
-  TRY(upload_f32(ctx, "hand_side_process.lh_embed", &ctx->lh));
-  return 0;
+  return upload_prefix_tables(ctx);
 }
 
 extern "C" int tamf_finalize_weights(tamf_ctx* ctx, int32_t max_timesteps, void* stream) {
@@ -1216,48 +1179,54 @@ extern "C" int tamf_finalize_weights(tamf_ctx* ctx, int32_t max_timesteps, void*
   if (max_timesteps <= 0 || max_timesteps > 5000) return fail(ctx, TAMF_ERR_INVALID, "max_timesteps must be in [1,5000]");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
-  for (const auto& kv : expected_shapes(ctx))
+  for (const auto& kv : ctx->expected)
     if (!ctx->raw.count(kv.first)) return fail(ctx, TAMF_ERR_MISSING, "missing checkpoint tensor: " + kv.first);
+  auto done = [&]() {
+    ctx->raw.clear();
+    ctx->expected.clear();
+    ctx->finalized = true;
+    if (!ctx->weight_note.empty()) ctx->err = ctx->weight_note;  // (readable through tamf_last_error after the successful call)
+    return 0;
+  };
   if (ctx->arch.kind == TAMF_KIND_E) {
     TRY(enc_finalize(ctx));
-    ctx->raw.clear();
-    ctx->finalized = true;
-    return 0;
+    return done();
   }
   const int d = ctx->d, ff = ctx->ff, F = ctx->F, prec = ctx->prec;
   auto R = [&](const std::string& n) -> const float* { return ctx->raw.at(n).data(); };
+  // Deferred LayerNorm: fold the gain AND the centring of the LayerNorm in front of a GEMM into its weight, W'' = W diag(gamma) (I - 1 1^T / d)
+  // (fp64: every row of W diag(gamma) minus its own mean), c2 = W beta + bias; the residual adds take gamma and beta + bias of the
+  // LayerNorm their residual input passes through.  W is [N][d]; the uploaded operand and c2 have Npad >= N rows, zero beyond N (the
+  // output head).  g = be = null (layer 0's attention block reads the encoder input itself): the plain weight.
+  auto fold = [&](const float* W, const float* bias, int N, int Npad, const float* g, const float* be, OperandBuf* ob, float** c2,
+                  const std::string& what) -> int {
+    std::vector<float> wf((size_t)Npad * d, 0.f), v2(Npad, 0.f);
+    for (int n = 0; n < N; ++n) {
+      double acc = bias[n], rowsum = 0.0;
+      for (int k = 0; k < d; ++k) {
+        if (g) rowsum += (double)W[(size_t)n * d + k] * g[k];
+        if (be) acc += (double)W[(size_t)n * d + k] * be[k];
+      }
+      const double shift = g ? rowsum / d : 0.0;  // W'' = W diag(gamma) (I - 1 1^T / d): every row minus its own mean
+      for (int k = 0; k < d; ++k) wf[(size_t)n * d + k] = g ? (float)((double)W[(size_t)n * d + k] * g[k] - shift) : W[(size_t)n * d + k];
+      v2[n] = (float)acc;
+    }
+    TRY(upload_operand(ctx, prec, wf.data(), Npad, d, d, ob, what.c_str()));
+    return dev_upload(ctx, c2, v2.data(), v2.size());
+  };
 
   for (int l = 0; l < ctx->L; ++l) {
     const std::string p = "seqTransEncoder.layers." + std::to_string(l);
     LayerW& w = ctx->layers[l];
     {
-      // Deferred LayerNorm: fold the gain AND the centring of the LayerNorm in front of a GEMM into its weight, W'' = W diag(gamma) (I - 1 1^T / d)
-      // (fp64: every row of W diag(gamma) minus its own mean), c2 = W beta + bias; the residual adds take gamma and beta + bias of the
-      // LayerNorm their residual input passes through.  Layer 0's attention block reads the encoder input itself: the plain weight.
       const std::string pp = "seqTransEncoder.layers." + std::to_string(l - 1);
       const float* g_in = l ? R(pp + ".norm2.weight") : nullptr;   // LayerNorm in front of this layer's attention block
       const float* be_in = l ? R(pp + ".norm2.bias") : nullptr;
       const float* g1 = R(p + ".norm1.weight");                    // ... in front of its feed-forward block
       const float* be1 = R(p + ".norm1.bias");
-      auto fold = [&](const float* W, const float* bias, int N, const float* g, const float* be, OperandBuf* ob, float** c2,
-                      const std::string& what) -> int {
-        std::vector<float> wf((size_t)N * d), v2(N);
-        for (int n = 0; n < N; ++n) {
-          double acc = bias[n], rowsum = 0.0;
-          for (int k = 0; k < d; ++k) {
-            if (g) rowsum += (double)W[(size_t)n * d + k] * g[k];
-            if (be) acc += (double)W[(size_t)n * d + k] * be[k];
-          }
-          const double shift = g ? rowsum / d : 0.0;  // W'' = W diag(gamma) (I - 1 1^T / d): every row minus its own mean
-          for (int k = 0; k < d; ++k) wf[(size_t)n * d + k] = g ? (float)((double)W[(size_t)n * d + k] * g[k] - shift) : W[(size_t)n * d + k];
-          v2[n] = (float)acc;
-        }
-        TRY(upload_operand(ctx, prec, wf.data(), N, d, d, ob, what.c_str()));
-        return dev_upload(ctx, c2, v2.data(), v2.size());
-      };
-      TRY(fold(R(p + ".self_attn.in_proj_weight"), R(p + ".self_attn.in_proj_bias"), 3 * d, g_in, be_in, &w.Win, &w.c2_in,
+      TRY(fold(R(p + ".self_attn.in_proj_weight"), R(p + ".self_attn.in_proj_bias"), 3 * d, 3 * d, g_in, be_in, &w.Win, &w.c2_in,
                p + ".self_attn.in_proj_weight"));
-      TRY(fold(R(p + ".linear1.weight"), R(p + ".linear1.bias"), ff, g1, be1, &w.W1, &w.c2_ff, p + ".linear1.weight"));
+      TRY(fold(R(p + ".linear1.weight"), R(p + ".linear1.bias"), ff, ff, g1, be1, &w.W1, &w.c2_ff, p + ".linear1.weight"));
       std::vector<float> ga(d), bb(d);
       for (int n = 0; n < d; ++n) {
         ga[n] = g_in ? g_in[n] : 1.0f;
@@ -1286,79 +1255,37 @@ extern "C" int tamf_finalize_weights(tamf_ctx* ctx, int32_t max_timesteps, void*
     const int qd = ctx->arch.obj_input_dim;
     const float* Wq = R("obj_input_process.poseEmbedding.weight");
     const float* bq = R("obj_input_process.poseEmbedding.bias");
+    const float* bh = isR ? R("h2o_dist_input_process.poseEmbedding.bias") : nullptr;
     std::vector<float> fused((size_t)d * ctx->XK, 0.f), cb(d), wct((size_t)qd * d);
-    for (int n = 0; n < d; ++n) {
+    for (int n = 0; n < d; ++n) {  // the bias: one term after the other (the encoder adds its two inside one loop: not shared)
       double acc_b = bm1[n];
       for (int j = 0; j < d; ++j) acc_b += (double)Wm1[(size_t)n * mk + j] * bp[j];
-      for (int k = 0; k < F; ++k) {
-        double a = 0;
-        for (int j = 0; j < d; ++j) a += (double)Wm1[(size_t)n * mk + j] * Wp[(size_t)j * F + k];
-        fused[(size_t)n * ctx->XK + k] = (float)a;
-      }
-      // the object half, hoisted out of the loop (cobj_kernel): W_m1[:, d:2d] . (W_q m + b_q) = Wc m + ..., Wc = W_m1[:, d:2d] . W_q
-      for (int k = 0; k < qd; ++k) {
-        double a = 0;
-        for (int j = 0; j < d; ++j) a += (double)Wm1[(size_t)n * mk + d + j] * Wq[(size_t)j * qd + k];
-        wct[(size_t)k * d + n] = (float)a;
-      }
       for (int j = 0; j < d; ++j) acc_b += (double)Wm1[(size_t)n * mk + d + j] * bq[j];
-      if (isR) {
-        const int Hd = ctx->arch.h2o_dim;
-        const float* Wh = R("h2o_dist_input_process.poseEmbedding.weight");
-        const float* bh = R("h2o_dist_input_process.poseEmbedding.bias");
+      if (isR)
         for (int j = 0; j < d; ++j) acc_b += (double)Wm1[(size_t)n * mk + 2 * d + j] * bh[j];
-        for (int k = 0; k < Hd; ++k) {
-          double a = 0;
-          for (int j = 0; j < d; ++j) a += (double)Wm1[(size_t)n * mk + 2 * d + j] * Wh[(size_t)j * Hd + k];
-          fused[(size_t)n * ctx->XK + F + k] = (float)a;
-        }
-      }
       cb[n] = (float)acc_b;
     }
+    compose_block(Wm1, mk, 0, d, Wp, F, fused.data(), ctx->XK, 1);
+    // the object half, hoisted out of the loop (cobj_kernel): W_m1[:, d:2d] . (W_q m + b_q) = Wc m + ..., Wc = W_m1[:, d:2d] . W_q
+    compose_block(Wm1, mk, d, d, Wq, qd, wct.data(), 1, d);
+    if (isR) compose_block(Wm1, mk, 2 * d, d, R("h2o_dist_input_process.poseEmbedding.weight"), ctx->arch.h2o_dim, fused.data() + F, ctx->XK, 1);
     TRY(upload_operand(ctx, prec, fused.data(), d, ctx->XK, ctx->XK, &ctx->Wfused, "input_merge.0.weight x poseEmbedding.weight (fused)"));
     TRY(dev_upload(ctx, &ctx->WcT, wct.data(), wct.size()));
     TRY(dev_upload(ctx, &ctx->bc, cb.data(), cb.size()));
   }
   TRY(upload_operand(ctx, prec, R("input_merge.2.weight"), d, d, d, &ctx->Wm2, "input_merge.2.weight"));
   TRY(upload_f32(ctx, "input_merge.2.bias", &ctx->bm2));
-  {
-    std::vector<float> wf((size_t)ctx->XN * d, 0.f), bfp(ctx->XN, 0.f);
-    memcpy(wf.data(), R("output_process.poseFinal.weight"), (size_t)F * d * 4);
-    memcpy(bfp.data(), R("output_process.poseFinal.bias"), (size_t)F * 4);
-    {  // the encoder's last LayerNorm, deferred into the head: W_f diag(gamma) (I - 1 1^T / d), c2 = W_f beta + b_f
-      const std::string pl = "seqTransEncoder.layers." + std::to_string(ctx->L - 1);
-      const float *g = R(pl + ".norm2.weight"), *be = R(pl + ".norm2.bias");
-      for (int n = 0; n < F; ++n) {
-        double acc = bfp[n], rowsum = 0.0;
-        for (int k = 0; k < d; ++k) {
-          acc += (double)wf[(size_t)n * d + k] * be[k];
-          rowsum += (double)wf[(size_t)n * d + k] * g[k];
-        }
-        for (int k = 0; k < d; ++k) wf[(size_t)n * d + k] = (float)((double)wf[(size_t)n * d + k] * g[k] - rowsum / d);
-        bfp[n] = (float)acc;
-      }
-    }
-    TRY(upload_operand(ctx, prec, wf.data(), ctx->XN, d, d, &ctx->Wf, "output_process.poseFinal.weight"));
-    TRY(dev_upload(ctx, &ctx->bf, bfp.data(), bfp.size()));
+  {  // the encoder's last LayerNorm, deferred into the head: W_f diag(gamma) (I - 1 1^T / d), c2 = W_f beta + b_f; XN rows, zero beyond F
+    const std::string pl = "seqTransEncoder.layers." + std::to_string(ctx->L - 1);
+    TRY(fold(R("output_process.poseFinal.weight"), R("output_process.poseFinal.bias"), F, ctx->XN, R(pl + ".norm2.weight"), R(pl + ".norm2.bias"),
+             &ctx->Wf, &ctx->bf, "output_process.poseFinal.weight"));
   }
   TRY(upload_f32(ctx, "sequence_pos_encoder.pe", &ctx->pe));
-  auto upload_T = [&](const std::string& name, int N, int K, float** p) -> int {  // W [N][K] -> W^T [K][N] (prefix_rows_kernel)
-    const float* W = R(name);
-    std::vector<float> t((size_t)N * K);
-    for (int n = 0; n < N; ++n)
-      for (int k = 0; k < K; ++k) t[(size_t)k * N + n] = W[(size_t)n * K + k];
-    return dev_upload(ctx, p, t.data(), t.size());
-  };
   if (ctx->arch.hand_shape_dim > 64 || ctx->arch.obj_input_dim > COBJ_QMAX || d > 1024)
     return fail(ctx, TAMF_ERR_INVALID, "hand_shape_dim > 64, obj_input_dim > 16 or latent_dim > 1024");
-  TRY(upload_T("hand_shape_process.shape_embed.weight", d, ctx->arch.hand_shape_dim, &ctx->WshapeT));
-  TRY(upload_f32(ctx, "hand_shape_process.shape_embed.bias", &ctx->bshape));
-  TRY(upload_T("obj_embed_process.embedding.weight", d, ctx->arch.obj_embed_dim, &ctx->WobjT));
-  TRY(upload_f32(ctx, "obj_embed_process.embedding.bias", &ctx->bobj));
-  TRY(upload_f32(ctx, "hand_side_process.rh_embed", &ctx->rh));
-  TRY(upload_f32(ctx, "hand_side_process.lh_embed", &ctx->lh));
+  TRY(upload_prefix_tables(ctx));
   if (ctx->has_t) {
-    TRY(upload_T("embed_text.weight", d, ctx->arch.clip_dim, &ctx->WtxtT));
+    TRY(upload_T(ctx, "embed_text.weight", d, ctx->arch.clip_dim, &ctx->WtxtT));
     TRY(upload_f32(ctx, "embed_text.bias", &ctx->btxt));
     TRY(upload_operand(ctx, TAMF_PREC_F32, R("embed_timestep.time_embed.0.weight"), d, d, d, &ctx->Wt1_f32, "embed_timestep.time_embed.0.weight"));
     TRY(upload_operand(ctx, TAMF_PREC_F32, R("embed_timestep.time_embed.2.weight"), d, d, d, &ctx->Wt2_f32, "embed_timestep.time_embed.2.weight"));
@@ -1377,10 +1304,7 @@ extern "C" int tamf_finalize_weights(tamf_ctx* ctx, int32_t max_timesteps, void*
     HIPCHK(ctx, gemm128<OpF32>(g2, e2, st));
   }
   HIPCHK(ctx, hipStreamSynchronize(st));
-  ctx->raw.clear();
-  ctx->finalized = true;
-  if (!ctx->weight_note.empty()) ctx->err = ctx->weight_note;  // (readable through tamf_last_error after the successful call)
-  return 0;
+  return done();
 }
 
 // destroy the executable graph once its last replay has finished (its launches may still be queued on the caller's stream)
@@ -1397,8 +1321,8 @@ static int retire_graph(tamf_ctx* ctx) {
 
 extern "C" int tamf_set_schedule(tamf_ctx* ctx, int32_t n_steps, const double* c1, const double* c2, const double* logvar) {
   TAMF_LAUNCH_LOCK;
-  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
-  if (!ctx || !c1 || !c2 || !logvar || n_steps <= 0) return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
+  TRY(need_kind(ctx, __func__, KIND_G | KIND_R));
+  if (!c1 || !c2 || !logvar || n_steps <= 0) return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   ctx->h_c1.resize(n_steps);
   ctx->h_c2.resize(n_steps);
@@ -1432,8 +1356,8 @@ extern "C" int tamf_set_schedule(tamf_ctx* ctx, int32_t n_steps, const double* c
 
 extern "C" int tamf_set_timestep_map(tamf_ctx* ctx, int32_t n_steps, const int32_t* map_host) {
   TAMF_LAUNCH_LOCK;
-  if (!ctx) return fail(ctx, TAMF_ERR_INVALID, "null ctx");
-  if (!ctx->finalized || !ctx->has_t) return fail(ctx, TAMF_ERR_STATE, "tamf_set_timestep_map needs a G context with finalised weights");
+  TRY(need_kind(ctx, __func__, KIND_G));
+  if (!ctx->finalized) return fail(ctx, TAMF_ERR_STATE, "tamf_set_timestep_map needs a G context with finalised weights");
   if (ctx->n_steps <= 0 || n_steps != ctx->n_steps) return fail(ctx, TAMF_ERR_STATE, "tamf_set_timestep_map: set the schedule of the same length first");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   TRY(retire_graph(ctx));  // (a captured loop holds the table pointer of its capture time)
@@ -1473,6 +1397,23 @@ extern "C" int tamf_set_timestep_map(tamf_ctx* ctx, int32_t n_steps, const int32
 // ------------------------------------------------------------------------------------------------
 // conditioning (step-invariant precompute, always exact fp32)
 // ------------------------------------------------------------------------------------------------
+// per-clip object counts (tamf_set_cond_ragged, tamf_encode; null: every clip has nobj objects): checked on the host, then copied to
+// the context's objnum_dev, which *cnt names for the kernels
+static int check_obj_num(tamf_ctx* ctx, const int32_t* obj_num_host, int B, int nobj) {
+  if (obj_num_host)
+    for (int b = 0; b < B; ++b)
+      if (obj_num_host[b] < 1 || obj_num_host[b] > nobj)
+        return fail(ctx, TAMF_ERR_INVALID, "obj_num[" + std::to_string(b) + "] = " + std::to_string(obj_num_host[b]) + " outside [1, nobj]");
+  return 0;
+}
+static int upload_obj_num(tamf_ctx* ctx, const int32_t* obj_num_host, int B, hipStream_t st, const int** cnt) {
+  *cnt = nullptr;
+  if (!obj_num_host) return 0;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->objnum_dev, obj_num_host, sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
+  *cnt = ctx->objnum_dev;
+  return 0;
+}
+
 extern "C" int tamf_set_cond(tamf_ctx* ctx, int32_t B, int32_t T, int32_t nobj, const float* text_emb_dev,
                              const uint8_t* hand_side_host, const float* shape_dev, const float* obj_emb_dev,
                              const float* obj_traj_dev, void* stream) {
@@ -1483,25 +1424,18 @@ extern "C" int tamf_set_cond_ragged(tamf_ctx* ctx, int32_t B, int32_t T, int32_t
                                     const float* text_emb_dev, const uint8_t* hand_side_host, const float* shape_dev,
                                     const float* obj_emb_dev, const float* obj_traj_dev, void* stream) {
   TAMF_LAUNCH_LOCK;
-  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
-  if (!ctx) return fail(ctx, TAMF_ERR_INVALID, "null ctx");
+  TRY(need_kind(ctx, __func__, KIND_G | KIND_R));
   if (!ctx->finalized) return fail(ctx, TAMF_ERR_STATE, "weights not finalised");
   if (B <= 0 || B > ctx->Bmax || T <= 0 || T > ctx->Tmax || nobj <= 0) return fail(ctx, TAMF_ERR_INVALID, "B/T/nobj out of range");
   if (!hand_side_host || !shape_dev || !obj_emb_dev || !obj_traj_dev || (ctx->has_t && !text_emb_dev))
     return fail(ctx, TAMF_ERR_INVALID, "null conditioning tensor");
   for (int b = 0; b < B; ++b)
     if (hand_side_host[b] > 1) return fail(ctx, TAMF_ERR_INVALID, "unexpected hand_side: " + std::to_string(hand_side_host[b]));
-  if (obj_num_host)
-    for (int b = 0; b < B; ++b)
-      if (obj_num_host[b] < 1 || obj_num_host[b] > nobj)
-        return fail(ctx, TAMF_ERR_INVALID, "obj_num[" + std::to_string(b) + "] = " + std::to_string(obj_num_host[b]) + " outside [1, nobj]");
+  TRY(check_obj_num(ctx, obj_num_host, B, nobj));
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   const int* cnt = nullptr;
-  if (obj_num_host) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->objnum_dev, obj_num_host, sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
-    cnt = ctx->objnum_dev;
-  }
+  TRY(upload_obj_num(ctx, obj_num_host, B, st, &cnt));
   const int d = ctx->d, P = ctx->P, ht = ctx->has_t, nrows = P - ht;
   ctx->B = B;
   ctx->T = T;
@@ -1773,10 +1707,9 @@ static int denoise_impl(tamf_ctx* ctx, const float* x, const int64_t* t_dev, flo
 
 extern "C" int tamf_denoise(tamf_ctx* ctx, const float* x_dev, const int64_t* t_dev, float* x0_out_dev, void* stream) {
   TAMF_LAUNCH_LOCK;
-  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
-  if (!ctx || !x_dev || !t_dev || !x0_out_dev) return fail(ctx, TAMF_ERR_INVALID, "null argument");
+  TRY(need_kind(ctx, __func__, KIND_G));
+  if (!x_dev || !t_dev || !x0_out_dev) return fail(ctx, TAMF_ERR_INVALID, "null argument");
   if (!ctx->cond_set) return fail(ctx, TAMF_ERR_STATE, "conditioning not set");
-  if (ctx->arch.kind != TAMF_KIND_G) return fail(ctx, TAMF_ERR_STATE, "tamf_denoise needs a G context");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   TAMF_WITH_OP(ctx->prec, return denoise_impl<Op>(ctx, x_dev, t_dev, x0_out_dev, st));
@@ -1800,10 +1733,9 @@ static int refine_impl(tamf_ctx* ctx, const float* x_in, const float* h2o, float
 extern "C" int tamf_refine(tamf_ctx* ctx, const float* sample_pose_repr_dev, const float* h2o_dist_dev, float* out_dev,
                            void* stream) {
   TAMF_LAUNCH_LOCK;
-  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
-  if (!ctx || !sample_pose_repr_dev || !h2o_dist_dev || !out_dev) return fail(ctx, TAMF_ERR_INVALID, "null argument");
+  TRY(need_kind(ctx, __func__, KIND_R));
+  if (!sample_pose_repr_dev || !h2o_dist_dev || !out_dev) return fail(ctx, TAMF_ERR_INVALID, "null argument");
   if (!ctx->cond_set) return fail(ctx, TAMF_ERR_STATE, "conditioning not set");
-  if (ctx->arch.kind != TAMF_KIND_R) return fail(ctx, TAMF_ERR_STATE, "tamf_refine needs an R context");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   TAMF_WITH_OP(ctx->prec, return refine_impl<Op>(ctx, sample_pose_repr_dev, h2o_dist_dev, out_dev, st));
@@ -1812,8 +1744,8 @@ extern "C" int tamf_refine(tamf_ctx* ctx, const float* sample_pose_repr_dev, con
 
 extern "C" int tamf_ddpm_step(tamf_ctx* ctx, const float* x_t_dev, const float* x0_dev, int32_t t, const float* noise_dev,
                               float* x_out_dev, int64_t n, void* stream) {
-  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
-  if (!ctx || !x_t_dev || !x0_dev || !x_out_dev || n <= 0) return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
+  TRY(need_kind(ctx, __func__, KIND_G | KIND_R));
+  if (!x_t_dev || !x0_dev || !x_out_dev || n <= 0) return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
   if (ctx->n_steps <= 0) return fail(ctx, TAMF_ERR_STATE, "schedule not set");
   if (t < 0 || t >= ctx->n_steps) return fail(ctx, TAMF_ERR_INVALID, "t out of range");
   if (t != 0 && !noise_dev) return fail(ctx, TAMF_ERR_INVALID, "noise required for t != 0");
@@ -1906,12 +1838,11 @@ static int loop_impl(tamf_ctx* ctx, const float* noise, uint64_t seed, int64_t c
 extern "C" int tamf_sample_loop(tamf_ctx* ctx, const float* noise_dev, uint64_t seed, int64_t clip_id_base, float* x0_out_dev,
                                 float* dump_dev, int32_t use_graph, void* stream) {
   TAMF_LAUNCH_LOCK;
-  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
-  if (!ctx || !x0_out_dev) return fail(ctx, TAMF_ERR_INVALID, "null argument");
+  TRY(need_kind(ctx, __func__, KIND_G));
+  if (!x0_out_dev) return fail(ctx, TAMF_ERR_INVALID, "null argument");
   if (!ctx->cond_set) return fail(ctx, TAMF_ERR_STATE, "conditioning not set");
   if (ctx->n_steps <= 0) return fail(ctx, TAMF_ERR_STATE, "schedule not set");
   if (ctx->n_steps > ctx->n_t) return fail(ctx, TAMF_ERR_STATE, "schedule longer than the timestep table (max_timesteps)");
-  if (ctx->arch.kind != TAMF_KIND_G) return fail(ctx, TAMF_ERR_STATE, "tamf_sample_loop needs a G context");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   TAMF_WITH_OP(ctx->prec, return loop_impl<Op>(ctx, noise_dev, seed, clip_id_base, x0_out_dev, dump_dev, use_graph, st));
@@ -1919,8 +1850,8 @@ extern "C" int tamf_sample_loop(tamf_ctx* ctx, const float* noise_dev, uint64_t 
 }
 
 extern "C" int tamf_get_status_flags(tamf_ctx* ctx, uint32_t* flags, int32_t clear, void* stream) {
-  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
-  if (!ctx || !flags) return fail(ctx, TAMF_ERR_INVALID, "null argument");
+  TRY(need_kind(ctx, __func__, KIND_G | KIND_R));
+  if (!flags) return fail(ctx, TAMF_ERR_INVALID, "null argument");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize((hipStream_t)stream));
   // this context's own word (per-context since round 4: another context on the device neither sees nor clears it)
@@ -1999,10 +1930,9 @@ static int profile_run(tamf_ctx* ctx, int32_t max_n, float* ms_host, double* flo
 extern "C" int tamf_step_profile(tamf_ctx* ctx, int32_t max_n, float* ms_host, double* flops_host, char* names_host,
                                  void* stream) {
   TAMF_LAUNCH_LOCK;
-  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
-  if (!ctx || !ms_host || !flops_host || !names_host || max_n <= 0) return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
+  TRY(need_kind(ctx, __func__, KIND_G));
+  if (!ms_host || !flops_host || !names_host || max_n <= 0) return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
   if (!ctx->cond_set || ctx->n_steps <= 0) return fail(ctx, TAMF_ERR_STATE, "conditioning / schedule not set");
-  if (ctx->arch.kind != TAMF_KIND_G) return fail(ctx, TAMF_ERR_STATE, "needs a G context");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(set_t_kernel, grid1d(ctx->B), dim3(256), 0, st, ctx->tcur, (const long long*)nullptr, ctx->n_steps / 2, ctx->B, ctx->n_t > 0 ? ctx->n_t : 1);
@@ -2016,11 +1946,10 @@ extern "C" int tamf_step_profile(tamf_ctx* ctx, int32_t max_n, float* ms_host, d
 extern "C" int tamf_refine_profile(tamf_ctx* ctx, const float* sample_pose_repr_dev, const float* h2o_dist_dev, float* out_dev,
                                    int32_t max_n, float* ms_host, double* flops_host, char* names_host, void* stream) {
   TAMF_LAUNCH_LOCK;
-  if (ctx && ctx->arch.kind == TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, std::string(__func__) + ": not available on a SegmentEncoder (TAMF_KIND_E) context");
-  if (!ctx || !sample_pose_repr_dev || !h2o_dist_dev || !out_dev || !ms_host || !flops_host || !names_host || max_n <= 0)
+  TRY(need_kind(ctx, __func__, KIND_R));
+  if (!sample_pose_repr_dev || !h2o_dist_dev || !out_dev || !ms_host || !flops_host || !names_host || max_n <= 0)
     return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
   if (!ctx->cond_set) return fail(ctx, TAMF_ERR_STATE, "conditioning not set");
-  if (ctx->arch.kind != TAMF_KIND_R) return fail(ctx, TAMF_ERR_STATE, "tamf_refine_profile needs an R context");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   return profile_run(ctx, max_n, ms_host, flops_host, names_host, st, [&]() {
@@ -2031,9 +1960,6 @@ extern "C" int tamf_refine_profile(tamf_ctx* ctx, const float* sample_pose_repr_
 }
 
 // ------------------------------------------------------------------------------------------------
-// geometry either side of the trunks
-// ------------------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------------------
 // SegmentEncoder forward (TAMF_KIND_E): two launches - the prefix rows (prefix_rows_kernel, shared with G / R) and the encoder
 // (encoder_kernel, tamf_encoder.h: one workgroup per clip)
 // ------------------------------------------------------------------------------------------------
@@ -2041,25 +1967,18 @@ extern "C" int tamf_encode(tamf_ctx* ctx, int32_t B, int32_t T, int32_t nobj, co
                            const float* shape_dev, const uint8_t* hand_side_dev, const float* obj_emb_dev, const float* obj_traj_dev,
                            float* encoding_out_dev, float* activation_out_dev, void* stream) {
   TAMF_LAUNCH_LOCK;
-  if (!ctx) return fail(ctx, TAMF_ERR_INVALID, "null ctx");
-  if (ctx->arch.kind != TAMF_KIND_E) return fail(ctx, TAMF_ERR_STATE, "tamf_encode needs a SegmentEncoder (TAMF_KIND_E) context");
+  TRY(need_kind(ctx, __func__, KIND_E));
   if (!ctx->finalized) return fail(ctx, TAMF_ERR_STATE, "weights not finalised");
   if (B <= 0 || B > ctx->Bmax || T <= 0 || T > ctx->Tmax || nobj <= 0)
     return fail(ctx, TAMF_ERR_INVALID, "B/T/nobj out of range (B = " + std::to_string(B) + " of max_batch " + std::to_string(ctx->Bmax) +
                                            ", T = " + std::to_string(T) + " of max_frames " + std::to_string(ctx->Tmax) + ")");
   if (!pose_repr_dev || !shape_dev || !hand_side_dev || !obj_emb_dev || !obj_traj_dev || !encoding_out_dev)
     return fail(ctx, TAMF_ERR_INVALID, "null tensor");
-  if (obj_num_host)
-    for (int b = 0; b < B; ++b)
-      if (obj_num_host[b] < 1 || obj_num_host[b] > nobj)
-        return fail(ctx, TAMF_ERR_INVALID, "obj_num[" + std::to_string(b) + "] = " + std::to_string(obj_num_host[b]) + " outside [1, nobj]");
+  TRY(check_obj_num(ctx, obj_num_host, B, nobj));
   HIPCHK(ctx, hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   const int* cnt = nullptr;
-  if (obj_num_host) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->objnum_dev, obj_num_host, sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
-    cnt = ctx->objnum_dev;
-  }
+  TRY(upload_obj_num(ctx, obj_num_host, B, st, &cnt));
   const int d = ctx->d, sd = ctx->arch.hand_shape_dim, od = ctx->arch.obj_embed_dim;
   PrefixArgs pa{};
   pa.side = hand_side_dev; pa.rh = ctx->rh; pa.lh = ctx->lh;
@@ -2082,9 +2001,7 @@ extern "C" int tamf_pose_decode(const float* pose_repr_dev, int64_t n_frames, in
   if (!pose_repr_dev || !quat_out_dev || n_frames <= 0 || n_joints <= 0) return fail(nullptr, TAMF_ERR_INVALID, "bad argument");
   hipLaunchKernelGGL(pose_decode_kernel, grid1d(n_frames * n_joints), dim3(256), 0, (hipStream_t)stream, pose_repr_dev,
                      tsl_out_dev, quat_out_dev, (long)n_frames, n_joints, 3 + 6 * n_joints);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(nullptr, TAMF_ERR_HIP, hipGetErrorString(e));
-  return 0;
+  return launched();
 }
 
 static int h2o_launch(const float* hand_verts_dev, const float* obj_traj_dev, const float* obj_points_dev,
@@ -2097,9 +2014,7 @@ static int h2o_launch(const float* hand_verts_dev, const float* obj_traj_dev, co
   if (B > 65535) return fail(nullptr, TAMF_ERR_INVALID, "batch too large for one launch");
   hipLaunchKernelGGL(h2o_dist_kernel, dim3(T, B), dim3(256), 0, (hipStream_t)stream, hand_verts_dev, obj_traj_dev,
                      obj_points_dev, (const int*)obj_num_dev, h2o_out_dev, frame_min_dev, T, V, nobj, P);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(nullptr, TAMF_ERR_HIP, hipGetErrorString(e));
-  return 0;
+  return launched();
 }
 
 extern "C" int tamf_h2o_dist(const float* hand_verts_dev, const float* obj_traj_dev, const float* obj_points_dev,
@@ -2126,9 +2041,7 @@ extern "C" int tamf_transform_points(const void* obj_traj_dev, const void* obj_p
   else
     hipLaunchKernelGGL((transform_points_kernel<float>), dim3(T, n_obj), dim3(256), 0, (hipStream_t)stream, (const float*)obj_traj_dev,
                        (const float*)obj_points_dev, (float*)out_dev, T, P);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(nullptr, TAMF_ERR_HIP, hipGetErrorString(e));
-  return 0;
+  return launched();
 }
 
 extern "C" int tamf_vertex_normals(const float* verts_dev, int64_t n_mesh, int32_t V, const int32_t* csr_off_dev,
@@ -2137,9 +2050,7 @@ extern "C" int tamf_vertex_normals(const float* verts_dev, int64_t n_mesh, int32
   if (n_mesh <= 0 || V <= 0) return fail(nullptr, TAMF_ERR_INVALID, "bad shape");
   hipLaunchKernelGGL(vertex_normals_kernel, grid1d((long)n_mesh * V), dim3(256), 0, (hipStream_t)stream, verts_dev, csr_off_dev,
                      csr_ent_dev, normals_out_dev, (long)n_mesh, V);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(nullptr, TAMF_ERR_HIP, hipGetErrorString(e));
-  return 0;
+  return launched();
 }
 
 extern "C" int tamf_mesh_contains(const double* verts_dev, const int32_t* faces_dev, int32_t n_faces, const double* points_dev,
@@ -2154,9 +2065,7 @@ extern "C" int tamf_mesh_contains(const double* verts_dev, const int32_t* faces_
   hipLaunchKernelGGL(mesh_contains_kernel, grid1d(n_points), dim3(256), 0, st, tri_workspace_dev, n_faces, points_dev,
                      (long)n_points, scale3[0], scale3[1], scale3[2], translate3[0], translate3[1], translate3[2],
                      (double)resolution, contains_out_dev);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(nullptr, TAMF_ERR_HIP, hipGetErrorString(e));
-  return 0;
+  return launched();
 }
 
 // PSKL-J score, device half (tamf_spectrum.h): one launch per PS_LENS clips - the lengths travel in the kernel arguments - each
@@ -2198,9 +2107,7 @@ extern "C" int tamf_power_spectrum_sum(const float* joints_dev, const int32_t* l
                        len_host ? 1 : 0, n, T, F, (accumulate || n0 > 0) ? 1 : 0, psd_sum_dev,
                        psd_clip_dev ? psd_clip_dev + (size_t)n0 * L * F : nullptr);
   }
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(nullptr, TAMF_ERR_HIP, hipGetErrorString(e));
-  return 0;
+  return launched();
 }
 
 #ifdef TAMF_TEST_HOOKS

@@ -157,6 +157,43 @@ def test_resize_keeps_weights():
     ctx.close()
 
 
+def test_a_resize_that_runs_out_of_memory_leaves_the_encoder_context_working_at_its_old_size(test_hooks):
+    """the E counterpart of the G test of this name in test_hip_guardbands.py: tamf_ctx_resize is one transactional body for every kind.
+    With either of an E context's two workspace allocations refused (injected on the host, nothing faults) the call reports it, the
+    old workspaces stay - dimensions, guard bands, the same bits from the same call - and a later resize that fits succeeds."""
+    import torch
+
+    from oakink2_tamf_amd.hip_backend import TamfError, set_guard_bytes
+
+    sd = seeded_state_dict(ARCH_ENCODER, seed=900)
+    inputs = seeded_inputs(2, 8, 2, seed=901)
+    args = (torch.from_numpy(inputs["pose_repr"]), torch.from_numpy(inputs["shape"]), inputs["hand_side"],
+            torch.from_numpy(inputs["obj_embedding"]), torch.from_numpy(inputs["obj_traj"]))
+    set_guard_bytes(4096)  # (every allocation from here on has a guard record: their number tells whether the context's lists are whole)
+    try:
+        ctx = _context(ARCH_ENCODER, sd, 2, 8)
+        ref_e, ref_a = (t.clone() for t in ctx.encode(*args))
+        n_guard = ctx.check_guards()
+        assert n_guard > 2  # the two workspaces + the weight tables
+        for k in (0, 1):  # an E context has exactly two workspace allocations
+            assert test_hooks.tamf_test_fail_alloc_after(k) == 0
+            try:
+                with pytest.raises(TamfError, match=r"keeps its 2 x 8 workspaces.*injected"):
+                    ctx.resize(4, 16)
+            finally:
+                assert test_hooks.tamf_test_fail_alloc_after(-1) == 0
+            assert (ctx.max_batch, ctx.max_frames) == (2, 8)
+            assert ctx.check_guards() == n_guard
+            enc, act = ctx.encode(*args)
+            assert torch.equal(enc, ref_e) and torch.equal(act, ref_a), k
+        ctx.resize(4, 16)
+        _check_against_restatement(ctx, sd, ARCH_ENCODER, seeded_inputs(4, 16, 2, seed=902))
+        assert ctx.check_guards() == n_guard
+        ctx.close()
+    finally:
+        set_guard_bytes(0)
+
+
 @pytest.mark.parametrize("change,max_frames,needle", [
     (dict(latent_dim=128), 100, "latent_dim must be 64"),
     (dict(num_heads=2), 100, "num_heads 4"),
