@@ -7,6 +7,7 @@ that description:
   EVAL     csrc/tamf_eval.hip -> libtamf_eval.so (include/tamf_eval.h: the context-free evaluation kernels of the SIV score)
   MANO     csrc/tamf_mano.hip -> libtamf_mano.so (include/tamf_mano.h: the native MANO hand layer)
   POINTENC csrc/tamf_pointenc.hip -> libtamf_pointenc.so (include/tamf_pointenc.h: the PointBERT point encoder behind obj_embedding)
+  TEXTENC  csrc/tamf_textenc.hip -> libtamf_textenc.so (include/tamf_textenc.h: the CLIP text tower behind text_embedding)
 Every library has its own sources, stamp and lock: building or loading one never touches another."""
 from __future__ import annotations
 
@@ -27,6 +28,7 @@ HOOKS_PATH = os.path.join(LIB_DIR, "libtamf_hip_hooks.so")  # test / measurement
 EVAL_LIB_PATH = os.path.join(LIB_DIR, "libtamf_eval.so")
 MANO_LIB_PATH = os.path.join(LIB_DIR, "libtamf_mano.so")
 POINTENC_LIB_PATH = os.path.join(LIB_DIR, "libtamf_pointenc.so")
+TEXTENC_LIB_PATH = os.path.join(LIB_DIR, "libtamf_textenc.so")
 
 EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_ctx_create", "tamf_ctx_resize", "tamf_ctx_destroy", "tamf_last_error", "tamf_load_weight", "tamf_finalize_weights",
@@ -49,6 +51,10 @@ MANO_EXPORTS = [  # include/tamf_mano.h: what libtamf_mano.so exports
 POINTENC_EXPORTS = [  # include/tamf_pointenc.h: what libtamf_pointenc.so exports
     "tamf_pointenc_last_error", "tamf_pointenc_model_create", "tamf_pointenc_load_weight", "tamf_pointenc_finalize", "tamf_pointenc_destroy",
     "tamf_pointenc_fold_bn", "tamf_pointenc_fps", "tamf_pointenc_group", "tamf_pointenc_workspace_bytes", "tamf_pointenc_encode",
+]
+TEXTENC_EXPORTS = [  # include/tamf_textenc.h: what libtamf_textenc.so exports
+    "tamf_textenc_last_error", "tamf_textenc_model_create", "tamf_textenc_load_weight", "tamf_textenc_finalize", "tamf_textenc_destroy",
+    "tamf_textenc_workspace_bytes", "tamf_textenc_encode",
 ]
 
 
@@ -244,13 +250,17 @@ MANO = Library("libtamf_mano", "tamf_mano.hip", ("tamf_mano.h", "tamf_hip.h"),  
 POINTENC = Library("libtamf_pointenc", "tamf_pointenc.hip", ("tamf_pointenc.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
                    (Output("libtamf_pointenc.so", (), POINTENC_EXPORTS),),
                    kernels=("_Z10fps_kernelILi8ELb1EE", "_Z10fps_kernelILi16ELb1EE", "_Z10fps_kernelILi32ELb0EE", "_Z12group_kernel", "_Z11gemm_kernel", "_Z11attn_kernel"))
+TEXTENC = Library("libtamf_textenc", "tamf_textenc.hip", ("tamf_textenc.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
+                  (Output("libtamf_textenc.so", (), TEXTENC_EXPORTS),),
+                  kernels=("_Z12embed_kernel", "_Z9ln_kernel", "_Z11gemm_kernel", "_Z11attn_kernel"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
+TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Every library, the sampler pair first, each only when ITS sources changed.  One library at a time.  Returns LIB_PATH."""
-    for lib in LIBRARIES + PREPROCESSING:
+    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING:
         lib.build(force, verbose)
     return LIB_PATH
 
@@ -302,6 +312,11 @@ def load_mano_lib() -> ctypes.CDLL:
 def load_pointenc() -> ctypes.CDLL:
     """libtamf_pointenc.so (include/tamf_pointenc.h).  Independent of the other libraries."""
     return _load(POINTENC, "libtamf_pointenc.so")
+
+
+def load_textenc() -> ctypes.CDLL:
+    """libtamf_textenc.so (include/tamf_textenc.h).  Independent of the other libraries."""
+    return _load(TEXTENC, "libtamf_textenc.so")
 
 
 def load_from(path: str) -> ctypes.CDLL:

@@ -18,10 +18,11 @@ Where the clips come from, in this order:
                                through dataset.interaction_segment.InteractionSegmentData + interaction_segment_collate, object
                                embeddings from --data.obj_embedding_prefix/<obj_id>.pt.  As in the reference the cache decides the
                                clips; --data.process_range and --data.data_prefix are accepted and not consulted (:312-324).
-The CLIP prompt: the cache carries `text` strings and the CLIP tower is not part of this build (its output is an input of the path,
-SURVEY.md 8c), so --data.text_embedding_filepath names a pickle {text: (512,) float32} (or an .npz with `text` / `embedding`)
-holding `clip_model.encode_text(...).float()` of every distinct prompt; without it the module's own CLIP branch is used if the
-`clip` package is importable.
+The CLIP prompt: the cache carries `text` strings and the CLIP tower's output is an input of the path, so
+--data.text_embedding_filepath names a pickle {text: (512,) float32} (or an .npz with `text` / `embedding`) holding
+`clip_model.encode_text(...).float()` of every distinct prompt - script/embed_text.sh (launch/embed_text.py, the native text tower)
+writes it from the cache and the user's CLIP files; without it the module's own CLIP branch is used if the `clip` package is
+importable.
 
 Differences: clips are sampled in batches (--runtime.batch_size, default 64) instead of one by one; workers default to ONE process
 per visible GPU (the reference's default is 8 workers on devices 0-3, launch/sample.py:114-127: with batched sampling a second
