@@ -11,10 +11,10 @@
 //                    key (distance bits | ~index) reduced by max over the wave and then over the 16 waves.
 //   group_kernel     the M nearest points of one centre per workgroup: N direct squared distances (the same expression) into LDS,
 //                    then M rounds of a 64-bit (distance bits | index) minimum - ascending (distance, index) order by construction.
-//   gemm_kernel      C = epi(A . W^T): 64 x 64 tile per workgroup, K in steps of 32 through LDS, v_mfma_f32_16x16x4_f32, k ascending.
-//                    An output element is ONE accumulator chain over its own A row and W row, so its bits do not depend on where
-//                    its row sits in the batch.  Epilogue: + bias, + a per-group row (the global half of the 512 -> 512 layer, applied
-//                    once per group), ReLU / exact-erf GELU, residual add, optional row remap (group g of cloud b -> token row 1 + g).
+//   PeEpi            the epilogue of csrc/tamf_f32_tower.h's f32_gemm_kernel (the shared fp32 GEMM; why an output element's bits do
+//                    not depend on where its row sits in the batch is explained there): + a per-group row (the global half of the
+//                    512 -> 512 layer, applied once per group), ReLU / exact-erf GELU, optional row remap (group g of cloud b -> token
+//                    row 1 + g), residual add.
 //   attn_kernel      softmax(scale q k^T) v for 16 queries of one (cloud, head) per workgroup, head dimension 64, up to 1025 tokens:
 //                    the 16 x T score panel in LDS (exact two-pass softmax, no running rescale), both contractions on the MFMA.
 //   row kernels      gather (centre subtracted from xyz only), max over a group, LayerNorm (optionally x += pos first), cls rows,
@@ -22,12 +22,10 @@
 //
 // Nothing is reduced with atomics and no launch parameter enters an operand: a cloud's output bits depend on the cloud and the model.
 #pragma once
-#include "tamf_device.h"
+#include "tamf_f32_tower.h"
 
-constexpr int PE_FPS_NT = 1024, PE_NT = 256;
-constexpr int PE_GT = 64, PE_GK = 32, PE_GLD = PE_GK + 4;  // gemm tile, k step, LDS row stride (floats)
-constexpr int PE_HD = 64;                                    // head dimension
-constexpr int PE_AQ = 16;                                    // queries per attention workgroup
+constexpr int PE_FPS_NT = 1024;
+constexpr int PE_AQ = 16;  // queries per attention workgroup
 // row stride of the attention score panel (floats): >= round_up(T, 4), and 4 mod 32 so that the 16 rows of an MFMA A fragment
 // fall into 16 different 4-bank groups
 __host__ __device__ inline int pe_att_ts(int T) { return (((T + 3) & ~3) + 31) / 32 * 32 + 4; }
@@ -112,10 +110,10 @@ __global__ __launch_bounds__(PE_FPS_NT) void fps_kernel(const float* __restrict_
 }
 
 // points (B, N, C), centre_idx (B, G) -> nbr_out (B, G, M): one workgroup per centre.  Dynamic LDS: N floats.  M <= N.
-__global__ __launch_bounds__(PE_NT) void group_kernel(const float* __restrict__ pts, const int* __restrict__ cidx, int* __restrict__ out,
-                                                      int N, int C, int G, int M) {
+__global__ __launch_bounds__(F32_NT) void group_kernel(const float* __restrict__ pts, const int* __restrict__ cidx, int* __restrict__ out,
+                                                       int N, int C, int G, int M) {
   extern __shared__ float pe_grp_lds[];
-  __shared__ unsigned long long red[2][PE_NT / 64];
+  __shared__ unsigned long long red[2][F32_NT / 64];
   float* d = pe_grp_lds;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x / G;
@@ -123,11 +121,11 @@ __global__ __launch_bounds__(PE_NT) void group_kernel(const float* __restrict__ 
   int ci = cidx[blockIdx.x];
   ci = (unsigned)ci < (unsigned)N ? ci : 0;
   const float cx = P[(long)ci * C], cy = P[(long)ci * C + 1], cz = P[(long)ci * C + 2];
-  for (int i = tid; i < N; i += PE_NT) d[i] = pe_sqdist(P[(long)i * C], P[(long)i * C + 1], P[(long)i * C + 2], cx, cy, cz);
+  for (int i = tid; i < N; i += F32_NT) d[i] = pe_sqdist(P[(long)i * C], P[(long)i * C + 1], P[(long)i * C + 2], cx, cy, cz);
   // (a thread reads and marks only its own elements until the reduction: no barrier needed before the first round)
   for (int m = 0; m < M; ++m) {
     unsigned long long best = ~0ull;
-    for (int i = tid; i < N; i += PE_NT) {
+    for (int i = tid; i < N; i += F32_NT) {
       const unsigned long long key = ((unsigned long long)__builtin_bit_cast(unsigned, d[i]) << 32) | (unsigned)i;
       best = key < best ? key : best;
     }
@@ -136,20 +134,20 @@ __global__ __launch_bounds__(PE_NT) void group_kernel(const float* __restrict__ 
     __syncthreads();
     unsigned long long r = red[m & 1][0];
 #pragma unroll
-    for (int w = 1; w < PE_NT / 64; ++w) {
+    for (int w = 1; w < F32_NT / 64; ++w) {
       const unsigned long long v = red[m & 1][w];
       r = v < r ? v : r;
     }
     const int sel = (int)(unsigned)(r & 0xFFFFFFFFu);
     if (tid == 0) out[(long)blockIdx.x * M + m] = sel;
-    if (sel % PE_NT == tid) d[sel] = __builtin_bit_cast(float, 0xFFFFFFFFu);  // above every distance key; its owner marks it
+    if (sel % F32_NT == tid) d[sel] = __builtin_bit_cast(float, 0xFFFFFFFFu);  // above every distance key; its owner marks it
   }
 }
 
 // x0 (B*G*M, Cp) = [xyz(nbr) - xyz(centre) | other channels of nbr | 0];  c0 (B*G, 4) = [xyz(centre) | 0]
-__global__ __launch_bounds__(PE_NT) void gather_kernel(const float* __restrict__ pts, const int* __restrict__ cidx, const int* __restrict__ nidx,
-                                                       float* __restrict__ x0, float* __restrict__ c0, long rows, int N, int C, int Cp, int G, int M) {
-  const long e = (long)blockIdx.x * PE_NT + threadIdx.x;
+__global__ __launch_bounds__(F32_NT) void gather_kernel(const float* __restrict__ pts, const int* __restrict__ cidx, const int* __restrict__ nidx,
+                                                        float* __restrict__ x0, float* __restrict__ c0, long rows, int N, int C, int Cp, int G, int M) {
+  const long e = (long)blockIdx.x * F32_NT + threadIdx.x;
   if (e >= rows * Cp) return;
   const long row = e / Cp;
   const int c = (int)(e % Cp);
@@ -166,8 +164,8 @@ __global__ __launch_bounds__(PE_NT) void gather_kernel(const float* __restrict__
 }
 
 // out (groups, W) = max over the M rows of each group of in (groups * M, W), rows in ascending order
-__global__ __launch_bounds__(PE_NT) void groupmax_kernel(const float* __restrict__ in, float* __restrict__ out, long groups, int M, int W) {
-  const long e = (long)blockIdx.x * PE_NT + threadIdx.x;
+__global__ __launch_bounds__(F32_NT) void groupmax_kernel(const float* __restrict__ in, float* __restrict__ out, long groups, int M, int W) {
+  const long e = (long)blockIdx.x * F32_NT + threadIdx.x;
   if (e >= groups * W) return;
   const long grp = e / W;
   const int c = (int)(e % W);
@@ -177,86 +175,27 @@ __global__ __launch_bounds__(PE_NT) void groupmax_kernel(const float* __restrict
   out[e] = m;
 }
 
-struct PeGemm {
-  const float* A;     // [M][lda]
-  const float* W;     // [N][ldw]
-  const float* bias;  // [N] or null
+// what follows acc + bias in the point encoder's products (f32_gemm_kernel<PeEpi>), in this order
+struct PeEpi {
   const float* radd;  // [M / rgrp][N] or null: added to every row of its group
-  float* C;           // [rows][ldc]
-  int lda, ldw, ldc, M, N, K;
-  int act;     // 0 none, 1 ReLU, 2 exact GELU
-  int rgrp;    // rows per radd row
-  int resid;   // C += result
-  int tokmap;  // > 0: output row = row + row / tokmap + 1 (group rows -> token rows behind each cloud's cls row)
+  int act;            // 0 none, 1 ReLU, 2 exact GELU
+  int rgrp;           // rows per radd row
+  int resid;          // C += result
+  int tokmap;         // > 0: output row = row + row / tokmap + 1 (group rows -> token rows behind each cloud's cls row)
+  __device__ void operator()(const F32Gemm& a, long row, int col, float v) const {
+    if (radd) v += radd[(row / rgrp) * a.N + col];
+    if (act == 1) v = fmaxf(v, 0.f);
+    else if (act == 2) v = gelu_erf(v);
+    const long orow = tokmap > 0 ? row + row / tokmap + 1 : row;
+    float* dst = a.C + orow * a.ldc + col;
+    *dst = resid ? *dst + v : v;
+  }
 };
 
-__global__ __launch_bounds__(PE_NT) void gemm_kernel(const PeGemm a) {
-  __shared__ float4 As4[PE_GT * PE_GLD / 4], Ws4[PE_GT * PE_GLD / 4];
-  float* As = reinterpret_cast<float*>(As4);
-  float* Ws = reinterpret_cast<float*>(Ws4);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
-  const int wm = wave >> 1, wn = wave & 1;
-  const long m0 = (long)blockIdx.x * PE_GT;
-  const int n0 = blockIdx.y * PE_GT;
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int k0 = 0; k0 < a.K; k0 += PE_GK) {
-    float4 ra[2], rw[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int idx = tid + j * PE_NT, row = idx >> 3, c4 = (idx & 7) * 4;
-      const bool kin = k0 + c4 < a.K;
-      ra[j] = (kin && m0 + row < a.M) ? *reinterpret_cast<const float4*>(a.A + (m0 + row) * a.lda + k0 + c4) : float4{0.f, 0.f, 0.f, 0.f};
-      rw[j] = (kin && n0 + row < a.N) ? *reinterpret_cast<const float4*>(a.W + (long)(n0 + row) * a.ldw + k0 + c4) : float4{0.f, 0.f, 0.f, 0.f};
-    }
-    __syncthreads();  // the previous step's reads are done
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int idx = tid + j * PE_NT, row = idx >> 3, c4 = (idx & 7) * 4;
-      *reinterpret_cast<float4*>(As + row * PE_GLD + c4) = ra[j];
-      *reinterpret_cast<float4*>(Ws + row * PE_GLD + c4) = rw[j];
-    }
-    __syncthreads();
-    const float* ap = As + (wm * 32 + r) * PE_GLD + g;
-    const float* wp = Ws + (wn * 32 + r) * PE_GLD + g;
-#pragma unroll
-    for (int kk = 0; kk < PE_GK; kk += 4) {
-      const float a0 = ap[kk], a1 = ap[16 * PE_GLD + kk], b0 = wp[kk], b1 = wp[16 * PE_GLD + kk];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = n0 + wn * 32 + j * 16 + r;
-      if (col >= a.N) continue;
-      const float bias = a.bias ? a.bias[col] : 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const long row = m0 + wm * 32 + i * 16 + 4 * g + e;
-        if (row >= a.M) continue;
-        float v = acc[i][j][e] + bias;
-        if (a.radd) v += a.radd[(row / a.rgrp) * a.N + col];
-        if (a.act == 1) v = fmaxf(v, 0.f);
-        else if (a.act == 2) v = gelu_erf(v);
-        const long orow = a.tokmap > 0 ? row + row / a.tokmap + 1 : row;
-        float* dst = a.C + orow * a.ldc + col;
-        *dst = a.resid ? *dst + v : v;
-      }
-    }
-}
-
-// x (rows, D): if pos: x += pos (stored); y = LayerNorm(x) * g + b, biased variance, two passes, eps 1e-5.  One wave per row.
-__global__ __launch_bounds__(PE_NT) void ln_kernel(float* __restrict__ x, const float* __restrict__ pos, const float* __restrict__ gam,
-                                                   const float* __restrict__ bet, float* __restrict__ y, long rows, int D) {
-  const long row = (long)blockIdx.x * (PE_NT / 64) + (threadIdx.x >> 6);
+// x (rows, D): if pos: x += pos (stored, fused into the pass that sums the row); y = LayerNorm(x) * g + b (f32_ln_row).  One wave per row.
+__global__ __launch_bounds__(F32_NT) void ln_kernel(float* __restrict__ x, const float* __restrict__ pos, const float* __restrict__ gam,
+                                                    const float* __restrict__ bet, float* __restrict__ y, long rows, int D) {
+  const long row = (long)blockIdx.x * (F32_NT / 64) + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
   float* xr = x + row * D;
@@ -269,20 +208,13 @@ __global__ __launch_bounds__(PE_NT) void ln_kernel(float* __restrict__ x, const 
     }
     s += v;
   }
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-  for (int c = lane; c < D; c += 64) {
-    const float dv = xr[c] - mean;
-    q += dv * dv;
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + 1e-5f);
-  for (int c = lane; c < D; c += 64) y[row * D + c] = (xr[c] - mean) * rstd * gam[c] + bet[c];
+  f32_ln_row(xr, s, gam, bet, y + row * D, D, lane);
 }
 
 // the cls rows: x[b][0] = cls_token, pos[b][0] = cls_pos
-__global__ __launch_bounds__(PE_NT) void cls_kernel(float* __restrict__ x, float* __restrict__ pos, const float* __restrict__ cls,
-                                                    const float* __restrict__ cpos, int B, int T, int D) {
-  const int e = blockIdx.x * PE_NT + threadIdx.x;
+__global__ __launch_bounds__(F32_NT) void cls_kernel(float* __restrict__ x, float* __restrict__ pos, const float* __restrict__ cls,
+                                                     const float* __restrict__ cpos, int B, int T, int D) {
+  const int e = blockIdx.x * F32_NT + threadIdx.x;
   if (e >= B * D) return;
   const int b = e / D, c = e % D;
   x[(long)b * T * D + c] = cls[c];
@@ -290,8 +222,8 @@ __global__ __launch_bounds__(PE_NT) void cls_kernel(float* __restrict__ x, float
 }
 
 // out (B, 2D) = cat(y[b][0], max over y[b][1:]), rows in ascending order
-__global__ __launch_bounds__(PE_NT) void pool_kernel(const float* __restrict__ y, float* __restrict__ out, int B, int T, int D) {
-  const int e = blockIdx.x * PE_NT + threadIdx.x;
+__global__ __launch_bounds__(F32_NT) void pool_kernel(const float* __restrict__ y, float* __restrict__ out, int B, int T, int D) {
+  const int e = blockIdx.x * F32_NT + threadIdx.x;
   if (e >= B * D) return;
   const int b = e / D, c = e % D;
   const float* p = y + (long)b * T * D + c;
@@ -303,9 +235,8 @@ __global__ __launch_bounds__(PE_NT) void pool_kernel(const float* __restrict__ y
 
 // qkv (B*T, 3D) with columns [q | k | v], each D = H * 64 wide, head h at h * 64  ->  o (B*T, D).
 // grid (ceil(T / 16), H, B).  Dynamic LDS: 16 * Ts + 16 floats, Ts = pe_att_ts(T).
-// The contraction index of q . k is permuted (lane group g covers k = 16g .. 16g + 15, so that a lane reads 64 contiguous bytes);
-// the order is the same for every score.
-__global__ __launch_bounds__(PE_NT) void attn_kernel(const float* __restrict__ qkv, float* __restrict__ o, int T, int D, float scale) {
+// Scores by f32_score_tile (the permuted contraction order is explained there), K and V read through L2.
+__global__ __launch_bounds__(F32_NT) void attn_kernel(const float* __restrict__ qkv, float* __restrict__ o, int T, int D, float scale) {
   extern __shared__ float4 pe_att_lds4[];
   float* S = reinterpret_cast<float*>(pe_att_lds4);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
@@ -314,30 +245,13 @@ __global__ __launch_bounds__(PE_NT) void attn_kernel(const float* __restrict__ q
   const int q0 = blockIdx.x * PE_AQ, h = blockIdx.y;
   const long base = (long)blockIdx.z * T;
   const long ld = 3L * D;
-  const float4 zero4 = {0.f, 0.f, 0.f, 0.f};
   // ---- scores ----
   float4 q4[4];
-  {
-    const bool in = q0 + r < T;
-    const float4* qp = reinterpret_cast<const float4*>(qkv + (base + q0 + r) * ld + h * PE_HD + g * 16);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) q4[j] = in ? qp[j] : zero4;
-  }
-  for (int nt = wave; nt * 16 < T; nt += PE_NT / 64) {
+  f32_load_q(q4, q0 + r < T, qkv + (base + q0 + r) * ld + h * F32_HD + g * 16);
+  for (int nt = wave; nt * 16 < T; nt += F32_NT / 64) {
     const int key = nt * 16 + r;
     const bool in = key < T;
-    const float4* kp = reinterpret_cast<const float4*>(qkv + (base + key) * ld + D + h * PE_HD + g * 16);
-    float4 k4[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) k4[j] = in ? kp[j] : zero4;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(q4[j].x, k4[j].x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(q4[j].y, k4[j].y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(q4[j].z, k4[j].z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(q4[j].w, k4[j].w, acc, 0, 0, 0);
-    }
+    const f32x4 acc = f32_score_tile(q4, qkv + (base + key) * ld + D + h * F32_HD + g * 16, in);
     if (in) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) S[(4 * g + e) * Ts + key] = acc[e] * scale;
@@ -366,7 +280,7 @@ __global__ __launch_bounds__(PE_NT) void attn_kernel(const float* __restrict__ q
   __syncthreads();
   // ---- output: wave w owns columns 16w .. 16w + 15 of the head; two accumulator chains (even / odd k steps), summed at the end ----
   {
-    const float* vp = qkv + base * ld + 2L * D + h * PE_HD + wave * 16 + r;
+    const float* vp = qkv + base * ld + 2L * D + h * F32_HD + wave * 16 + r;
     const float* sp = S + r * Ts + g;
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     int k0 = 0;
@@ -384,7 +298,7 @@ __global__ __launch_bounds__(PE_NT) void attn_kernel(const float* __restrict__ q
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int q = q0 + 4 * g + e;
-      if (q < T) o[(base + q) * D + h * PE_HD + wave * 16 + r] = (acc0[e] + acc1[e]) * inv[4 * g + e];
+      if (q < T) o[(base + q) * D + h * F32_HD + wave * 16 + r] = (acc0[e] + acc1[e]) * inv[4 * g + e];
     }
   }
 }

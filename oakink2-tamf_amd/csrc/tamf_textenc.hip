@@ -3,36 +3,15 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "tamf_textenc.h"
+#include "tamf_weights.h"
 
-static thread_local std::string g_te_error;
-
-static int fail(int code, const std::string& msg) {
-  g_te_error = msg;
-  return code;
-}
-
-extern "C" const char* tamf_textenc_last_error(void) { return g_te_error.c_str(); }
+extern "C" const char* tamf_textenc_last_error(void) { return g_error.c_str(); }
 
 namespace {
-
-struct Tensor {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-  bool loaded = false;
-  bool fp16 = false;  // one of the tensors the reference's convert_weights turns into fp16
-  long numel() const {
-    long n = 1;
-    for (int64_t s : shape) n *= s;
-    return n;
-  }
-};
 
 // offsets (floats) into the device weight buffer; every tensor starts on a multiple of 4 floats
 struct LayerOff {
@@ -49,25 +28,17 @@ struct Workspace {
 
 struct tamf_textenc_model {
   tamf_textenc_config cfg{};
-  std::vector<std::string> order;  // the keys in state-dict order
-  std::map<std::string, Tensor> t;
+  WeightTable w;  // closed once finalize has checked (and possibly rounded) the tensors, whether or not the upload succeeds; fp16: one of
+                  // the tensors the reference's convert_weights turns into fp16
   long tok = 0, pos = 0, proj = 0, gf = 0, bf = 0;
   std::vector<LayerOff> lo;
   float* dev = nullptr;
-  bool sealed = false;     // finalize has checked (and possibly rounded) the tensors: nothing can be loaded any more
-  bool finalized = false;  // ... and uploaded them
+  bool finalized = false;  // the weights are on the device
   // the row map of a call goes through pinned host memory; the event says when the previous call's upload has left it
   int32_t* stage = nullptr;
   long stage_words = 0;
   hipEvent_t stage_ev = nullptr;
 };
-
-static void declare(tamf_textenc_model* m, const std::string& key, std::vector<int64_t> shape, bool fp16) {
-  m->order.push_back(key);
-  Tensor& t = m->t[key];
-  t.shape = std::move(shape);
-  t.fp16 = fp16;
-}
 
 extern "C" int tamf_textenc_model_create(const tamf_textenc_config* c, tamf_textenc_model** model_out) {
   if (!c || !model_out) return fail(TAMF_ERR_INVALID, "null argument");
@@ -76,120 +47,80 @@ extern "C" int tamf_textenc_model_create(const tamf_textenc_config* c, tamf_text
   if (c->context_length < 2 || c->context_length > TE_CTX_MAX)
     return fail(TAMF_ERR_INVALID, "context_length = " + std::to_string(c->context_length) + " outside [2, 128]");
   if (c->width < 64 || c->width > 1024 || c->width % 64) return fail(TAMF_ERR_INVALID, "width = " + std::to_string(c->width) + ": a multiple of 64 up to 1024");
-  if (c->num_heads * TE_HD != c->width) return fail(TAMF_ERR_INVALID, "num_heads = " + std::to_string(c->num_heads) + ": the head dimension must be 64 (width / 64 heads)");
+  if (c->num_heads * F32_HD != c->width) return fail(TAMF_ERR_INVALID, "num_heads = " + std::to_string(c->num_heads) + ": the head dimension must be 64 (width / 64 heads)");
   if (c->num_layers < 1) return fail(TAMF_ERR_INVALID, "num_layers = " + std::to_string(c->num_layers) + ": at least 1");
   if (c->embed_dim < 16 || c->embed_dim > 1024 || c->embed_dim % 16) return fail(TAMF_ERR_INVALID, "embed_dim = " + std::to_string(c->embed_dim) + ": a multiple of 16 up to 1024");
   tamf_textenc_model* m = new tamf_textenc_model;
   m->cfg = *c;
   const int64_t W = c->width, E = c->embed_dim;
-  declare(m, "token_embedding.weight", {c->vocab_size, W}, false);
-  declare(m, "positional_embedding", {c->context_length, W}, false);
+  m->w.declare("token_embedding.weight", {c->vocab_size, W}, false);
+  m->w.declare("positional_embedding", {c->context_length, W}, false);
   for (int l = 0; l < c->num_layers; ++l) {
     const std::string p = "transformer.resblocks." + std::to_string(l) + ".";
-    declare(m, p + "ln_1.weight", {W}, false);
-    declare(m, p + "ln_1.bias", {W}, false);
-    declare(m, p + "attn.in_proj_weight", {3 * W, W}, true);
-    declare(m, p + "attn.in_proj_bias", {3 * W}, true);
-    declare(m, p + "attn.out_proj.weight", {W, W}, true);
-    declare(m, p + "attn.out_proj.bias", {W}, true);
-    declare(m, p + "ln_2.weight", {W}, false);
-    declare(m, p + "ln_2.bias", {W}, false);
-    declare(m, p + "mlp.c_fc.weight", {4 * W, W}, true);
-    declare(m, p + "mlp.c_fc.bias", {4 * W}, true);
-    declare(m, p + "mlp.c_proj.weight", {W, 4 * W}, true);
-    declare(m, p + "mlp.c_proj.bias", {W}, true);
+    m->w.declare(p + "ln_1.weight", {W}, false);
+    m->w.declare(p + "ln_1.bias", {W}, false);
+    m->w.declare(p + "attn.in_proj_weight", {3 * W, W}, true);
+    m->w.declare(p + "attn.in_proj_bias", {3 * W}, true);
+    m->w.declare(p + "attn.out_proj.weight", {W, W}, true);
+    m->w.declare(p + "attn.out_proj.bias", {W}, true);
+    m->w.declare(p + "ln_2.weight", {W}, false);
+    m->w.declare(p + "ln_2.bias", {W}, false);
+    m->w.declare(p + "mlp.c_fc.weight", {4 * W, W}, true);
+    m->w.declare(p + "mlp.c_fc.bias", {4 * W}, true);
+    m->w.declare(p + "mlp.c_proj.weight", {W, 4 * W}, true);
+    m->w.declare(p + "mlp.c_proj.bias", {W}, true);
   }
-  declare(m, "ln_final.weight", {W}, false);
-  declare(m, "ln_final.bias", {W}, false);
-  declare(m, "text_projection", {W, E}, true);
+  m->w.declare("ln_final.weight", {W}, false);
+  m->w.declare("ln_final.bias", {W}, false);
+  m->w.declare("text_projection", {W, E}, true);
   *model_out = m;
   return 0;
 }
 
-static std::string shape_str(const int64_t* s, int n) {
-  std::string r = "(";
-  for (int i = 0; i < n; ++i) r += (i ? ", " : "") + std::to_string(s[i]);
-  return r + ")";
-}
-
 extern "C" int tamf_textenc_load_weight(tamf_textenc_model* m, const char* key, const float* host, int32_t ndim, const int64_t* shape) {
-  if (!m || !key || !host || (ndim > 0 && !shape) || ndim < 0) return fail(TAMF_ERR_INVALID, "null argument");
-  if (m->sealed) return fail(TAMF_ERR_STATE, "the model is finalised");
-  auto it = m->t.find(key);
-  if (it == m->t.end()) return fail(TAMF_ERR_INVALID, std::string("unknown key '") + key + "'");
-  Tensor& t = it->second;
-  if ((size_t)ndim != t.shape.size() || !std::equal(t.shape.begin(), t.shape.end(), shape))
-    return fail(TAMF_ERR_INVALID, std::string(key) + ": expected shape " + shape_str(t.shape.data(), (int)t.shape.size()) + ", got " + shape_str(shape, ndim));
-  t.data.assign(host, host + t.numel());
-  t.loaded = true;
-  return 0;
+  return m ? m->w.load(key, host, ndim, shape) : fail(TAMF_ERR_INVALID, "null argument");
 }
 
 extern "C" int tamf_textenc_finalize(tamf_textenc_model* m, int32_t round_fp16) {
   if (!m) return fail(TAMF_ERR_INVALID, "null argument");
-  if (m->sealed) return fail(TAMF_ERR_STATE, "the model is finalised already");
-  for (const std::string& k : m->order) {
-    const Tensor& t = m->t[k];
-    if (!t.loaded) return fail(TAMF_ERR_MISSING, "missing key '" + k + "'");
-    for (float v : t.data)
-      if (!std::isfinite(v)) return fail(TAMF_ERR_RANGE, k + ": holds a non-finite value");
-  }
+  if (m->w.closed) return fail(TAMF_ERR_STATE, "the model is finalised already");
+  if (int rc = m->w.require_loaded_and_finite()) return rc;
   if (round_fp16)
-    for (const std::string& k : m->order) {
-      Tensor& t = m->t[k];
+    for (const std::string& k : m->w.order) {
+      Tensor& t = m->w[k];
       if (!t.fp16) continue;
       for (float& v : t.data) {
         v = (float)(_Float16)v;  // round to nearest even, as torch's .half()
         if (!std::isfinite(v)) return fail(TAMF_ERR_RANGE, k + ": holds a value beyond the fp16 range");
       }
     }
-  m->sealed = true;
+  m->w.closed = true;
   const int W = m->cfg.width, E = m->cfg.embed_dim, L = m->cfg.num_layers;
-  std::vector<float> h;
-  auto reserve = [&](long n) {
-    const long off = (long)h.size();
-    h.resize((size_t)(off + (n + 3) / 4 * 4), 0.f);
-    return off;
-  };
-  auto put = [&](const std::string& k) {
-    Tensor& t = m->t[k];
-    const long off = reserve(t.numel());
-    std::copy(t.data.begin(), t.data.end(), h.begin() + off);
-    std::vector<float>().swap(t.data);  // the host copy is not needed any more
-    return off;
-  };
-  m->tok = put("token_embedding.weight"), m->pos = put("positional_embedding");
+  Packer pk{m->w, true};
+  std::vector<float>& h = pk.h;
+  m->tok = pk.put("token_embedding.weight"), m->pos = pk.put("positional_embedding");
   m->lo.resize(L);
   for (int l = 0; l < L; ++l) {
     const std::string p = "transformer.resblocks." + std::to_string(l) + ".";
     LayerOff& o = m->lo[l];
-    o.g1 = put(p + "ln_1.weight"), o.b1 = put(p + "ln_1.bias");
-    o.wqkv = put(p + "attn.in_proj_weight"), o.bqkv = put(p + "attn.in_proj_bias");
-    o.wout = put(p + "attn.out_proj.weight"), o.bout = put(p + "attn.out_proj.bias");
-    o.g2 = put(p + "ln_2.weight"), o.b2 = put(p + "ln_2.bias");
-    o.wfc = put(p + "mlp.c_fc.weight"), o.bfc = put(p + "mlp.c_fc.bias");
-    o.wproj = put(p + "mlp.c_proj.weight"), o.bproj = put(p + "mlp.c_proj.bias");
+    o.g1 = pk.put(p + "ln_1.weight"), o.b1 = pk.put(p + "ln_1.bias");
+    o.wqkv = pk.put(p + "attn.in_proj_weight"), o.bqkv = pk.put(p + "attn.in_proj_bias");
+    o.wout = pk.put(p + "attn.out_proj.weight"), o.bout = pk.put(p + "attn.out_proj.bias");
+    o.g2 = pk.put(p + "ln_2.weight"), o.b2 = pk.put(p + "ln_2.bias");
+    o.wfc = pk.put(p + "mlp.c_fc.weight"), o.bfc = pk.put(p + "mlp.c_fc.bias");
+    o.wproj = pk.put(p + "mlp.c_proj.weight"), o.bproj = pk.put(p + "mlp.c_proj.bias");
   }
-  m->gf = put("ln_final.weight"), m->bf = put("ln_final.bias");
+  m->gf = pk.put("ln_final.weight"), m->bf = pk.put("ln_final.bias");
   {  // text_projection (W, E) is stored transposed, (E, W): the tail is the same C = A . W^T as every other product
-    Tensor& t = m->t["text_projection"];
-    m->proj = reserve((long)E * W);
+    Tensor& t = m->w["text_projection"];
+    m->proj = pk.reserve((long)E * W);
     for (int k = 0; k < W; ++k)
       for (int n = 0; n < E; ++n) h[m->proj + (long)n * W + k] = t.data[(long)k * E + n];
     std::vector<float>().swap(t.data);
   }
-  hipError_t e = hipMalloc((void**)&m->dev, h.size() * sizeof(float));
-  if (e != hipSuccess) {
-    m->dev = nullptr;
-    return fail(e == hipErrorOutOfMemory ? TAMF_ERR_NOMEM : TAMF_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-  }
-  e = hipMemcpy(m->dev, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&m->stage_ev, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    (void)hipFree(m->dev);
-    m->dev = nullptr;
+  if (int rc = upload(h, &m->dev, "upload", [m] { return hipEventCreateWithFlags(&m->stage_ev, hipEventDisableTiming); })) {
     m->stage_ev = nullptr;
-    return fail(TAMF_ERR_HIP, std::string("upload: ") + hipGetErrorString(e));
+    return rc;
   }
   m->finalized = true;
   return 0;
@@ -206,43 +137,24 @@ extern "C" int tamf_textenc_destroy(tamf_textenc_model* m) {
   return 0;
 }
 
-// dynamic LDS above 64 KiB has to be allowed per kernel (an attribute of the kernel on the current device; setting it again costs
-// a host call, no device work)
-template <class K>
-static hipError_t allow_lds(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 namespace {
 
 Workspace workspace(const tamf_textenc_model* m, long B, long M) {
   const long W = m->cfg.width;
   Workspace w;
-  long o = 0;
-  auto take = [&](long n) {
-    const long at = o;
-    o += (n + 3) / 4 * 4;
-    return at;
-  };
+  Carver cv;
   // (the five parts of the row map are contiguous: one upload)
   w.ids = 0, w.pos = M, w.start = 2 * M, w.len = 2 * M + B, w.eot = 2 * M + 2 * B;
   w.map_words = 2 * M + 3 * B;
-  take(w.map_words);
-  w.x = take(M * W), w.y = take(M * W), w.qkv = take(M * 3 * W), w.ao = take(M * W), w.hh = take(M * 4 * W), w.t = take(B * W);
-  w.total = o;
+  cv.take(w.map_words);
+  w.x = cv.take(M * W), w.y = cv.take(M * W), w.qkv = cv.take(M * 3 * W), w.ao = cv.take(M * W), w.hh = cv.take(M * 4 * W), w.t = cv.take(B * W);
+  w.total = cv.total;
   return w;
 }
 
 void gemm(hipStream_t st, const float* A, int lda, long M, const float* W, int ldw, int N, int K, const float* bias, float* C, int ldc, int act, int resid) {
-  TeGemm a;
-  a.A = A, a.W = W, a.bias = bias, a.C = C;
-  a.lda = lda, a.ldw = ldw, a.ldc = ldc, a.M = (int)M, a.N = N, a.K = K;
-  a.act = act, a.resid = resid;
-  hipLaunchKernelGGL(gemm_kernel, dim3((unsigned)((M + TE_GT - 1) / TE_GT), (unsigned)((N + TE_GT - 1) / TE_GT)), dim3(TE_NT), 0, st, a);
+  f32_gemm(st, F32Gemm{A, W, bias, C, lda, ldw, ldc, (int)M, N, K}, TeEpi{act, resid});
 }
-
-unsigned blocks(long n) { return (unsigned)((n + TE_NT - 1) / TE_NT); }
 
 bool rows_ok(const tamf_textenc_model* m, long B, long M) {
   return B >= 1 && B <= 65535 && M >= B && M <= B * m->cfg.context_length && M * 4 * m->cfg.width < (1L << 31);
@@ -260,7 +172,6 @@ extern "C" int tamf_textenc_encode(tamf_textenc_model* m, const int32_t* tokens_
   if (!m) return fail(TAMF_ERR_INVALID, "null argument");
   if (!m->finalized) return fail(TAMF_ERR_STATE, "the weights are not finalised");
   if (!tokens_host || !out_dev || !workspace_dev) return fail(TAMF_ERR_INVALID, "null argument");
-  if ((uintptr_t)workspace_dev & 15) return fail(TAMF_ERR_INVALID, "the workspace must be 16-byte aligned");
   if (B < 1 || B > 65535) return fail(TAMF_ERR_INVALID, "B = " + std::to_string(B) + " outside [1, 65535]");
   const int ctx = m->cfg.context_length, V = m->cfg.vocab_size, W = m->cfg.width, E = m->cfg.embed_dim, H = m->cfg.num_heads;
   // every row's EOT position: the first index of its largest id
@@ -281,8 +192,7 @@ extern "C" int tamf_textenc_encode(tamf_textenc_model* m, const int32_t* tokens_
   }
   if (!rows_ok(m, B, M)) return fail(TAMF_ERR_INVALID, "B = " + std::to_string(B) + " is too large for one call: split the batch");
   const Workspace ws = workspace(m, B, M);
-  if (workspace_bytes < ws.total * (int64_t)sizeof(float))
-    return fail(TAMF_ERR_INVALID, "workspace of " + std::to_string(workspace_bytes) + " bytes, need " + std::to_string(ws.total * sizeof(float)));
+  if (int rc = check_workspace(workspace_dev, workspace_bytes, ws.total)) return rc;
   const int Lp = (Lmax + 15) / 16 * 16;
   const size_t att_lds = (size_t)te_att_lds_floats(Lp) * sizeof(float);
   hipError_t e = allow_lds(attn_kernel, att_lds);
@@ -318,21 +228,21 @@ extern "C" int tamf_textenc_encode(tamf_textenc_model* m, const int32_t* tokens_
   if (e == hipSuccess) e = hipEventRecord(m->stage_ev, st);
   if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("row map upload: ") + hipGetErrorString(e));
   const float* p = m->dev;
-  hipLaunchKernelGGL(embed_kernel, dim3(blocks(M * W)), dim3(TE_NT), 0, st, p + m->tok, p + m->pos, wi + ws.ids, wi + ws.pos, w + ws.x, M, W);
-  const unsigned ln_blocks = (unsigned)((M + TE_NT / 64 - 1) / (TE_NT / 64));
+  hipLaunchKernelGGL(embed_kernel, dim3(blocks(M * W, F32_NT)), dim3(F32_NT), 0, st, p + m->tok, p + m->pos, wi + ws.ids, wi + ws.pos, w + ws.x, M, W);
+  const unsigned ln_blocks = blocks(M, F32_NT / 64);
   const float scale = 0.125f;  // 64^-0.5
   for (int l = 0; l < m->cfg.num_layers; ++l) {
     const LayerOff& lo = m->lo[l];
-    hipLaunchKernelGGL(ln_kernel, dim3(ln_blocks), dim3(TE_NT), 0, st, w + ws.x, (const int*)nullptr, p + lo.g1, p + lo.b1, w + ws.y, M, W);
+    hipLaunchKernelGGL(ln_kernel, dim3(ln_blocks), dim3(F32_NT), 0, st, w + ws.x, (const int*)nullptr, p + lo.g1, p + lo.b1, w + ws.y, M, W);
     gemm(st, w + ws.y, W, M, p + lo.wqkv, W, 3 * W, W, p + lo.bqkv, w + ws.qkv, 3 * W, 0, 0);
-    hipLaunchKernelGGL(attn_kernel, dim3((unsigned)H, (unsigned)B), dim3(TE_NT), att_lds, st, w + ws.qkv, wi + ws.start, wi + ws.len, w + ws.ao, W, Lp, scale);
+    hipLaunchKernelGGL(attn_kernel, dim3((unsigned)H, (unsigned)B), dim3(F32_NT), att_lds, st, w + ws.qkv, wi + ws.start, wi + ws.len, w + ws.ao, W, Lp, scale);
     gemm(st, w + ws.ao, W, M, p + lo.wout, W, W, W, p + lo.bout, w + ws.x, W, 0, 1);
-    hipLaunchKernelGGL(ln_kernel, dim3(ln_blocks), dim3(TE_NT), 0, st, w + ws.x, (const int*)nullptr, p + lo.g2, p + lo.b2, w + ws.y, M, W);
+    hipLaunchKernelGGL(ln_kernel, dim3(ln_blocks), dim3(F32_NT), 0, st, w + ws.x, (const int*)nullptr, p + lo.g2, p + lo.b2, w + ws.y, M, W);
     gemm(st, w + ws.y, W, M, p + lo.wfc, W, 4 * W, W, p + lo.bfc, w + ws.hh, 4 * W, 1, 0);
     gemm(st, w + ws.hh, 4 * W, M, p + lo.wproj, 4 * W, W, 4 * W, p + lo.bproj, w + ws.x, W, 0, 1);
   }
   // the tail: ln_final on the B EOT rows, then the projection
-  hipLaunchKernelGGL(ln_kernel, dim3((unsigned)((B + TE_NT / 64 - 1) / (TE_NT / 64))), dim3(TE_NT), 0, st, w + ws.x, wi + ws.eot, p + m->gf, p + m->bf, w + ws.t, (long)B, W);
+  hipLaunchKernelGGL(ln_kernel, dim3(blocks(B, F32_NT / 64)), dim3(F32_NT), 0, st, w + ws.x, wi + ws.eot, p + m->gf, p + m->bf, w + ws.t, (long)B, W);
   gemm(st, w + ws.t, W, B, p + m->proj, W, E, W, nullptr, out_dev, E, 0, 0);
   e = hipGetLastError();
   if (e != hipSuccess) return fail(TAMF_ERR_HIP, hipGetErrorString(e));

@@ -8,6 +8,8 @@ that description:
   MANO     csrc/tamf_mano.hip -> libtamf_mano.so (include/tamf_mano.h: the native MANO hand layer)
   POINTENC csrc/tamf_pointenc.hip -> libtamf_pointenc.so (include/tamf_pointenc.h: the PointBERT point encoder behind obj_embedding)
   TEXTENC  csrc/tamf_textenc.hip -> libtamf_textenc.so (include/tamf_textenc.h: the CLIP text tower behind text_embedding)
+POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
+score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
 Every library has its own sources, stamp and lock: building or loading one never touches another."""
 from __future__ import annotations
 
@@ -249,10 +251,10 @@ MANO = Library("libtamf_mano", "tamf_mano.hip", ("tamf_mano.h", "tamf_hip.h"),  
                kernels=("_Z19mano_forward_kernelILi1EE", "_Z19mano_forward_kernelILi2EE", "_Z19mano_forward_kernelILi4EE"))
 POINTENC = Library("libtamf_pointenc", "tamf_pointenc.hip", ("tamf_pointenc.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
                    (Output("libtamf_pointenc.so", (), POINTENC_EXPORTS),),
-                   kernels=("_Z10fps_kernelILi8ELb1EE", "_Z10fps_kernelILi16ELb1EE", "_Z10fps_kernelILi32ELb0EE", "_Z12group_kernel", "_Z11gemm_kernel", "_Z11attn_kernel"))
+                   kernels=("_Z10fps_kernelILi8ELb1EE", "_Z10fps_kernelILi16ELb1EE", "_Z10fps_kernelILi32ELb0EE", "_Z12group_kernel", "_Z15f32_gemm_kernelI5PeEpiE", "_Z11attn_kernel"))
 TEXTENC = Library("libtamf_textenc", "tamf_textenc.hip", ("tamf_textenc.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
                   (Output("libtamf_textenc.so", (), TEXTENC_EXPORTS),),
-                  kernels=("_Z12embed_kernel", "_Z9ln_kernel", "_Z11gemm_kernel", "_Z11attn_kernel"))
+                  kernels=("_Z12embed_kernel", "_Z9ln_kernel", "_Z15f32_gemm_kernelI5TeEpiE", "_Z11attn_kernel"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)

@@ -14,10 +14,12 @@ generator; default: index 0), so an embedding is a function of the cloud, the we
 from __future__ import annotations
 
 import ctypes
-from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_void_p
+from ctypes import POINTER, c_float, c_int32, c_int64, c_void_p
 from typing import Dict, List, Mapping, Optional, Tuple
 
 import numpy as np
+
+from ._native import NativeLibrary, NativeModel
 
 PREFIX = "module.point_encoder."
 # PointTransformer_8192point_2layer.yaml as model/pointbert/cfg.py:load_cfg switches it (point_dims 6, use_max_pool)
@@ -81,37 +83,21 @@ def map_checkpoint(state_dict: Mapping, cfg: Mapping[str, int]):
     return {k: got[k] for k in want if k in got}, missing, unexpected
 
 
-_bound = None
-
-
-def _bind():
-    global _bound
-    if _bound is None:
-        from .. import _lib
-
-        lib = _lib.load_pointenc()
-        lib.tamf_pointenc_last_error.restype = c_char_p
-        lib.tamf_pointenc_model_create.argtypes = [POINTER(_Config), POINTER(c_void_p)]
-        lib.tamf_pointenc_load_weight.argtypes = [c_void_p, c_char_p, c_void_p, c_int32, POINTER(c_int64)]
-        lib.tamf_pointenc_finalize.argtypes = [c_void_p]
-        lib.tamf_pointenc_destroy.argtypes = [c_void_p]
-        lib.tamf_pointenc_fold_bn.argtypes = [POINTER(c_float)] * 6 + [c_int32] * 3 + [POINTER(c_float)] * 2
-        lib.tamf_pointenc_fps.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]
-        lib.tamf_pointenc_group.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]
-        lib.tamf_pointenc_workspace_bytes.argtypes = [c_void_p, c_int32]
-        lib.tamf_pointenc_workspace_bytes.restype = c_int64
-        lib.tamf_pointenc_encode.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]
-        _bound = lib
-    return _bound
-
-
 class PointEncoderError(RuntimeError):
     pass
 
 
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise PointEncoderError(f"libtamf_pointenc: {lib.tamf_pointenc_last_error().decode()} (status {rc})")
+def _argtypes(lib) -> None:
+    lib.tamf_pointenc_finalize.argtypes = [c_void_p]
+    lib.tamf_pointenc_fold_bn.argtypes = [POINTER(c_float)] * 6 + [c_int32] * 3 + [POINTER(c_float)] * 2
+    lib.tamf_pointenc_fps.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]
+    lib.tamf_pointenc_group.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]
+    lib.tamf_pointenc_workspace_bytes.argtypes = [c_void_p, c_int32]
+    lib.tamf_pointenc_encode.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]
+
+
+_NATIVE = NativeLibrary("pointenc", PointEncoderError, _argtypes)
+_bind, _check = _NATIVE.bind, _NATIVE.check
 
 
 def fold_bn(w, b, gamma, beta, running_mean, running_var, ld_out: Optional[int] = None):
@@ -129,13 +115,15 @@ def fold_bn(w, b, gamma, beta, running_mean, running_var, ld_out: Optional[int] 
     def fp(a):
         return a.ctypes.data_as(POINTER(c_float))
 
-    _check(lib, lib.tamf_pointenc_fold_bn(fp(w), *[fp(v) for v in vec], out_ch, in_ch, ld, fp(wo), fp(bo)))
+    _check(lib.tamf_pointenc_fold_bn(fp(w), *[fp(v) for v in vec], out_ch, in_ch, ld, fp(wo), fp(bo)))
     return wo, bo
 
 
-class HipPointEncoder:
+class HipPointEncoder(NativeModel):
     """The point encoder on the GPU.  `cfg`: the fields of DEFAULT_CFG (missing ones take their defaults).  A missing kernel library
     or a device that is no GPU is an error; there is no torch fall-back."""
+
+    _native = _NATIVE
 
     def __init__(self, cfg: Optional[Mapping] = None, device="cuda"):
         import torch
@@ -148,7 +136,7 @@ class HipPointEncoder:
         self._model = c_void_p()
         self._loaded = False
         c = _Config(**{k: self.cfg[k] for k in CFG_FIELDS})
-        _check(self._lib, self._lib.tamf_pointenc_model_create(ctypes.byref(c), ctypes.byref(self._model)))
+        _check(self._lib.tamf_pointenc_model_create(ctypes.byref(c), ctypes.byref(self._model)))
 
     @property
     def out_dim(self) -> int:
@@ -158,19 +146,9 @@ class HipPointEncoder:
     def load_state_dict(self, state_dict: Mapping) -> None:
         """names without the `module.point_encoder.` prefix -> tensors / arrays.  A missing name, a wrong shape, an unknown name or a
         non-finite value raises PointEncoderError (num_batches_tracked counters are skipped)."""
-        import torch
-
         if self._loaded:
             raise PointEncoderError("the weights are loaded already")
-        for k, v in state_dict.items():
-            if k.endswith(".num_batches_tracked"):
-                continue
-            a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            shape = (c_int64 * max(a.ndim, 1))(*a.shape)
-            _check(self._lib, self._lib.tamf_pointenc_load_weight(self._model, k.encode(), a.ctypes.data, a.ndim, shape))
-        with torch.cuda.device(self.device):
-            _check(self._lib, self._lib.tamf_pointenc_finalize(self._model))
+        self._load_weights({k: v for k, v in state_dict.items() if not k.endswith(".num_batches_tracked")})
         self._loaded = True
 
     def load_checkpoint(self, path) -> Tuple[List[str], List[str]]:
@@ -247,7 +225,7 @@ class HipPointEncoder:
         start = self._indices("start_index", self._start(B, N, start_index, seed), (B,), N)
         out = torch.empty((B, G), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            _check(self._lib, self._lib.tamf_pointenc_fps(p.data_ptr(), start.data_ptr(), B, N, C, G, out.data_ptr(), _stream_ptr(self.device)))
+            _check(self._lib.tamf_pointenc_fps(p.data_ptr(), start.data_ptr(), B, N, C, G, out.data_ptr(), _stream_ptr(self.device)))
         return out.long()
 
     def group(self, points, centre_idx, group_size: Optional[int] = None):
@@ -268,7 +246,7 @@ class HipPointEncoder:
         G = int(ci.shape[1])
         out = torch.empty((B, G, M), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            _check(self._lib, self._lib.tamf_pointenc_group(p.data_ptr(), ci.data_ptr(), B, N, C, G, M, out.data_ptr(), _stream_ptr(self.device)))
+            _check(self._lib.tamf_pointenc_group(p.data_ptr(), ci.data_ptr(), B, N, C, G, M, out.data_ptr(), _stream_ptr(self.device)))
         return out.long()
 
     def encode_groups(self, points, centre_idx, nbr_idx):
@@ -292,7 +270,7 @@ class HipPointEncoder:
             ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
             for b0 in range(0, B, nb):
                 n = min(nb, B - b0)
-                _check(self._lib, self._lib.tamf_pointenc_encode(self._model, p[b0:].data_ptr(), ci[b0:].data_ptr(), ni[b0:].data_ptr(), n, N,
+                _check(self._lib.tamf_pointenc_encode(self._model, p[b0:].data_ptr(), ci[b0:].data_ptr(), ni[b0:].data_ptr(), n, N,
                                                                 out[b0:].data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(self.device)))
         return out
 
@@ -304,20 +282,6 @@ class HipPointEncoder:
         return self.encode_groups(p, centre, self.group(p, centre))
 
     __call__ = encode
-
-    def close(self) -> None:
-        if getattr(self, "_model", None) is not None and self._model.value:
-            import torch
-
-            torch.cuda.synchronize(self.device)
-            self._lib.tamf_pointenc_destroy(self._model)
-            self._model = c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 __all__ = ["HipPointEncoder", "PointEncoderError", "DEFAULT_CFG", "PREFIX", "make_cfg", "expected_shapes", "map_checkpoint", "fold_bn"]

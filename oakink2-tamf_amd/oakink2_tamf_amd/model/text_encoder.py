@@ -12,12 +12,13 @@ the real checkpoint is not verified."""
 from __future__ import annotations
 
 import ctypes
-from ctypes import POINTER, c_char_p, c_int32, c_int64, c_void_p
+from ctypes import c_int32, c_int64, c_void_p
 from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
 from ..hip_backend import TamfError
+from ._native import NativeLibrary, NativeModel
 
 # ViT-B/32's text side
 DEFAULT_CFG = dict(vocab_size=49408, context_length=77, width=512, num_heads=8, num_layers=12, embed_dim=512)
@@ -77,30 +78,14 @@ def map_state_dict(state_dict: Mapping, cfg: Mapping[str, int]):
     return {k: got[k] for k in want if k in got}, missing, ignored
 
 
-_bound = None
+def _argtypes(lib) -> None:
+    lib.tamf_textenc_finalize.argtypes = [c_void_p, c_int32]
+    lib.tamf_textenc_workspace_bytes.argtypes = [c_void_p, c_int32, c_int64]
+    lib.tamf_textenc_encode.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p]
 
 
-def _bind():
-    global _bound
-    if _bound is None:
-        from .. import _lib
-
-        lib = _lib.load_textenc()
-        lib.tamf_textenc_last_error.restype = c_char_p
-        lib.tamf_textenc_model_create.argtypes = [POINTER(_Config), POINTER(c_void_p)]
-        lib.tamf_textenc_load_weight.argtypes = [c_void_p, c_char_p, c_void_p, c_int32, POINTER(c_int64)]
-        lib.tamf_textenc_finalize.argtypes = [c_void_p, c_int32]
-        lib.tamf_textenc_destroy.argtypes = [c_void_p]
-        lib.tamf_textenc_workspace_bytes.argtypes = [c_void_p, c_int32, c_int64]
-        lib.tamf_textenc_workspace_bytes.restype = c_int64
-        lib.tamf_textenc_encode.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p]
-        _bound = lib
-    return _bound
-
-
-def _check(lib, rc: int) -> None:
-    if rc != 0:
-        raise TextEncoderError(f"libtamf_textenc: {lib.tamf_textenc_last_error().decode()} (status {rc})")
+_NATIVE = NativeLibrary("textenc", TextEncoderError, _argtypes)
+_bind, _check = _NATIVE.bind, _NATIVE.check
 
 
 def eot_positions(ids: np.ndarray) -> np.ndarray:
@@ -108,9 +93,11 @@ def eot_positions(ids: np.ndarray) -> np.ndarray:
     return np.argmax(np.asarray(ids), axis=1)
 
 
-class HipClipTextEncoder:
+class HipClipTextEncoder(NativeModel):
     """The text tower on the GPU.  `cfg`: the fields of DEFAULT_CFG (missing ones take their defaults).  A missing kernel library or
     a device that is no GPU is an error; there is no torch fall-back."""
+
+    _native = _NATIVE
 
     def __init__(self, cfg: Optional[Mapping] = None, device="cuda:0", round_fp16: bool = True):
         import torch
@@ -124,7 +111,7 @@ class HipClipTextEncoder:
         self._model = c_void_p()
         self._loaded = False
         c = _Config(**{k: self.cfg[k] for k in CFG_FIELDS})
-        _check(self._lib, self._lib.tamf_textenc_model_create(ctypes.byref(c), ctypes.byref(self._model)))
+        _check(self._lib.tamf_textenc_model_create(ctypes.byref(c), ctypes.byref(self._model)))
 
     @property
     def out_dim(self) -> int:
@@ -137,8 +124,6 @@ class HipClipTextEncoder:
         ignored and returned."""
         import logging
 
-        import torch
-
         if self._loaded:
             raise TextEncoderError("the weights are loaded already")
         sd, missing, ignored = map_state_dict(state_dict, self.cfg)
@@ -146,13 +131,7 @@ class HipClipTextEncoder:
             raise TextEncoderError(f"text encoder: missing keys {missing}")
         if ignored:
             logging.getLogger(__name__).info("text encoder: %d keys ignored (%s ...)", len(ignored), ", ".join(ignored[:4]))
-        for k, v in sd.items():
-            a = v.detach().float().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            shape = (c_int64 * max(a.ndim, 1))(*a.shape)
-            _check(self._lib, self._lib.tamf_textenc_load_weight(self._model, k.encode(), a.ctypes.data, a.ndim, shape))
-        with torch.cuda.device(self.device):
-            _check(self._lib, self._lib.tamf_textenc_finalize(self._model, int(self.round_fp16)))
+        self._load_weights(sd, int(self.round_fp16))
         self._loaded = True
         return ignored
 
@@ -194,7 +173,7 @@ class HipClipTextEncoder:
                 n = min(MAX_PROMPTS_PER_CALL, B - b0)
                 nbytes = int(self._lib.tamf_textenc_workspace_bytes(self._model, n, int(rows[b0: b0 + n].sum())))
                 ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)  # (freed stream-ordered by torch's allocator)
-                _check(self._lib, self._lib.tamf_textenc_encode(self._model, a[b0:].ctypes.data, n, out[b0:].data_ptr(), ws.data_ptr(), nbytes,
+                _check(self._lib.tamf_textenc_encode(self._model, a[b0:].ctypes.data, n, out[b0:].data_ptr(), ws.data_ptr(), nbytes,
                                                                _stream_ptr(self.device)))
         return out
 
@@ -208,20 +187,6 @@ class HipClipTextEncoder:
         ids = np.zeros((len(texts), ctx), dtype=np.int32)
         ids[:, :n] = tokenizer.tokenize(list(texts), context_length=n, truncate=True)
         return self.encode_tokens(ids)
-
-    def close(self) -> None:
-        if getattr(self, "_model", None) is not None and self._model.value:
-            import torch
-
-            torch.cuda.synchronize(self.device)
-            self._lib.tamf_textenc_destroy(self._model)
-            self._model = c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 __all__ = ["HipClipTextEncoder", "TextEncoderError", "DEFAULT_CFG", "CKPT_PREFIX", "make_cfg", "expected_shapes", "map_state_dict", "is_fp16_key",

@@ -140,6 +140,31 @@ def test_an_edit_makes_only_its_own_library_stale(edited, owner, tmp_path, monke
     assert _lib.SAMPLER.stale()
 
 
+def test_an_edit_to_the_shared_tower_header_makes_exactly_the_two_encoders_stale(tmp_path, monkeypatch):
+    """csrc/tamf_f32_tower.h belongs to the point and text encoders and to no other library; on the same kind of copied tree"""
+    import shutil
+
+    from oakink2_tamf_amd import _lib
+
+    for name, src in (("csrc", _lib.CSRC), ("include", _lib.INCLUDE)):
+        shutil.copytree(src, tmp_path / name)
+    monkeypatch.setattr(_lib, "CSRC", str(tmp_path / "csrc"))
+    monkeypatch.setattr(_lib, "INCLUDE", str(tmp_path / "include"))
+    monkeypatch.setattr(_lib, "LIB_DIR", str(tmp_path / "lib"))
+    os.makedirs(_lib.LIB_DIR)
+    libs = _lib.LIBRARIES + _lib.PREPROCESSING + _lib.TEXT_PREPROCESSING
+    for lib in libs:
+        for p in lib.paths:
+            open(p, "w").close()
+        with open(lib.stamp_path, "w") as f:
+            f.write(lib.digest() + "\n")
+    assert not any(lib.stale() for lib in libs)
+    with open(tmp_path / "csrc" / "tamf_f32_tower.h", "a") as f:
+        f.write("\n// edited\n")
+    assert [lib.stale() for lib in libs] == [False, False, False, True, True]
+    assert libs[3:] == (_lib.POINTENC, _lib.TEXTENC)
+
+
 def test_no_gpu_fails_loudly():
     from oakink2_tamf_amd.hip_backend import TamfContext, TamfError
 

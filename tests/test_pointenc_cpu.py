@@ -92,7 +92,10 @@ def test_header_exports_and_source_closure():
         hdr = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     assert set(re.findall(r"\b(tamf_[a-z0-9_]+)\s*\(", hdr)) == set(_lib.POINTENC_EXPORTS) and len(set(_lib.POINTENC_EXPORTS)) == len(_lib.POINTENC_EXPORTS)
     assert not set(_lib.POINTENC_EXPORTS) & set(_lib.EXPORTS + _lib.EVAL_EXPORTS + _lib.HOOK_EXPORTS + _lib.MANO_EXPORTS)
-    assert _lib.POINTENC.sources == ["tamf_device.h", "tamf_pointenc.h", "tamf_pointenc.hip"]  # no other library's sources
+    # no other library's sources: tamf_f32_tower.h and tamf_weights.h are common ground of the two encoders, like tamf_device.h
+    assert _lib.POINTENC.sources == ["tamf_device.h", "tamf_f32_tower.h", "tamf_pointenc.h", "tamf_pointenc.hip", "tamf_weights.h"]
+    assert not [s for lib in _lib.LIBRARIES for s in lib.sources if s in ("tamf_f32_tower.h", "tamf_weights.h")]
+    assert not [s for s in _lib.TEXTENC.sources if s.startswith("tamf_pointenc")] and not [s for s in _lib.POINTENC.sources if s.startswith("tamf_textenc")]
     assert not [s for lib in _lib.LIBRARIES for s in lib.sources if s.startswith("tamf_pointenc")]
     assert _lib.POINTENC in _lib.PREPROCESSING and _lib.POINTENC.paths == [_lib.POINTENC_LIB_PATH]
     assert len({lib.stamp_path for lib in _lib.LIBRARIES + _lib.PREPROCESSING}) == 4
@@ -115,6 +118,74 @@ def test_encoder_needs_a_gpu():
     else:
         with pytest.raises(TamfError, match="no CPU fallback"):
             HipPointEncoder(F.CASES["tiny"][0])
+
+
+TAMF_ERR_INVALID, TAMF_ERR_STATE, TAMF_ERR_MISSING, TAMF_ERR_RANGE = -1, -2, -4, -6  # (include/tamf_hip.h; pinned by test_textenc_cpu.py)
+
+
+def test_host_side_errors_need_no_gpu():
+    """the library's host paths through ctypes, as tests/test_textenc_cpu.py pins the text tower's.  Unlike the text tower, the point
+    encoder becomes final only with a successful upload: without a device it can still be loaded into."""
+    import ctypes
+    from ctypes import c_int64, c_void_p
+
+    from oakink2_tamf_amd.model import point_encoder as P
+
+    lib = P._bind()
+    err = lambda: lib.tamf_pointenc_last_error().decode()  # noqa: E731
+    cfg = F.CASES["tiny"][0]
+    sd = F.seeded_state_dict(cfg, 1)
+
+    def create(**over):
+        model = c_void_p()
+        return lib.tamf_pointenc_model_create(ctypes.byref(P._Config(**dict(cfg, **over))), ctypes.byref(model)), model
+
+    def load(model, key, a):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        return lib.tamf_pointenc_load_weight(model, key.encode(), a.ctypes.data, a.ndim, (c_int64 * max(a.ndim, 1))(*a.shape))
+
+    for over, word in ((dict(point_dims=4), "point_dims"), (dict(trans_dim=96), "trans_dim"), (dict(num_heads=3), "num_heads"), (dict(depth=0), "depth"),
+                       (dict(num_group=1025), "num_group"), (dict(group_size=7), "group_size"), (dict(encoder_dims=40), "encoder_dims")):
+        rc, model = create(**over)
+        assert rc == TAMF_ERR_INVALID and not model.value and word in err(), (over, err())
+    rc, model = create()
+    assert rc == 0 and model.value
+    assert load(model, "visual.proj", np.zeros((4, 4))) == TAMF_ERR_INVALID and err() == "unknown key 'visual.proj'"
+    assert load(model, "encoder.first_conv.1.num_batches_tracked", np.zeros(())) == TAMF_ERR_INVALID and "unknown key" in err()
+    assert load(model, "reduce_dim.weight", np.zeros((64, 128))) == TAMF_ERR_INVALID and err() == "reduce_dim.weight: expected shape (128, 64), got (64, 128)"
+    assert load(model, "cls_token", np.zeros((128,))) == TAMF_ERR_INVALID and err() == "cls_token: expected shape (1, 1, 128), got (128)"
+    assert lib.tamf_pointenc_load_weight(model, b"norm.bias", None, 1, (c_int64 * 1)(128)) == TAMF_ERR_INVALID and err() == "null argument"
+    # nothing to encode with: encode before finalize is a state error; a missing tensor and a non-finite one are named by finalize
+    enc = lib.tamf_pointenc_encode(model, c_void_p(16), c_void_p(16), c_void_p(16), 1, 250, c_void_p(16), c_void_p(16), 1 << 20, None)
+    assert enc == TAMF_ERR_STATE and "not finalised" in err()
+    for k, v in sd.items():
+        if k != "blocks.blocks.1.mlp.fc2.bias":
+            assert load(model, k, v) == 0, err()
+    assert lib.tamf_pointenc_finalize(model) == TAMF_ERR_MISSING and err() == "missing key 'blocks.blocks.1.mlp.fc2.bias'"
+    bad = sd["norm.weight"].copy()
+    bad[3] = np.inf
+    assert load(model, "blocks.blocks.1.mlp.fc2.bias", sd["blocks.blocks.1.mlp.fc2.bias"]) == 0 and load(model, "norm.weight", bad) == 0
+    assert lib.tamf_pointenc_finalize(model) == TAMF_ERR_RANGE and err() == "norm.weight: holds a non-finite value"
+    var = sd["encoder.first_conv.1.running_var"].copy()
+    var[5] = -1.0  # finite, but BatchNorm cannot be folded
+    assert load(model, "norm.weight", sd["norm.weight"]) == 0 and load(model, "encoder.first_conv.1.running_var", var) == 0
+    assert lib.tamf_pointenc_finalize(model) == TAMF_ERR_RANGE and "BatchNorm channel 5" in err()
+    assert lib.tamf_pointenc_encode(model, c_void_p(16), c_void_p(16), c_void_p(16), 1, 250, c_void_p(16), c_void_p(16), 1 << 20, None) == TAMF_ERR_STATE
+    # a complete, finite set: final with the upload - where there is no device, finalize fails and the model still takes tensors
+    assert load(model, "encoder.first_conv.1.running_var", sd["encoder.first_conv.1.running_var"]) == 0
+    rc = lib.tamf_pointenc_finalize(model)
+    if torch.cuda.is_available():
+        assert rc == 0 and load(model, "norm.bias", sd["norm.bias"]) == TAMF_ERR_STATE and "finalised" in err()
+        assert lib.tamf_pointenc_finalize(model) == TAMF_ERR_STATE and "finalised already" in err()
+    else:
+        assert rc < 0 and "hipMalloc" in err()
+        assert load(model, "norm.bias", sd["norm.bias"]) == 0
+        assert lib.tamf_pointenc_encode(model, c_void_p(16), c_void_p(16), c_void_p(16), 1, 250, c_void_p(16), c_void_p(16), 1 << 20, None) == TAMF_ERR_STATE
+    G, M, D, E = cfg["num_group"], cfg["group_size"], cfg["trans_dim"], cfg["encoder_dims"]
+    assert lib.tamf_pointenc_workspace_bytes(None, 1) == 0 and lib.tamf_pointenc_workspace_bytes(model, 0) == 0 and lib.tamf_pointenc_workspace_bytes(model, -3) == 0
+    one, two = lib.tamf_pointenc_workspace_bytes(model, 1), lib.tamf_pointenc_workspace_bytes(model, 2)
+    assert one >= 4 * (G * M * (4 + 128 + 256 + 512 + E) + (G + 1) * 10 * D) and one % 16 == 0 and one < two <= 2 * one
+    assert lib.tamf_pointenc_destroy(model) == 0 and lib.tamf_pointenc_destroy(None) == 0
 
 
 def _run(*args):

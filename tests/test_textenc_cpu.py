@@ -102,7 +102,10 @@ def test_library_description():
         hdr = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     assert set(re.findall(r"\b(tamf_[a-z0-9_]+)\s*\(", hdr)) == set(_lib.TEXTENC_EXPORTS) and len(set(_lib.TEXTENC_EXPORTS)) == len(_lib.TEXTENC_EXPORTS)
     assert not set(_lib.TEXTENC_EXPORTS) & set(_lib.EXPORTS + _lib.EVAL_EXPORTS + _lib.HOOK_EXPORTS + _lib.MANO_EXPORTS + _lib.POINTENC_EXPORTS)
-    assert _lib.TEXTENC.sources == ["tamf_device.h", "tamf_textenc.h", "tamf_textenc.hip"]  # no other library's sources
+    # no other library's sources: tamf_f32_tower.h and tamf_weights.h are common ground of the two encoders, like tamf_device.h
+    assert _lib.TEXTENC.sources == ["tamf_device.h", "tamf_f32_tower.h", "tamf_textenc.h", "tamf_textenc.hip", "tamf_weights.h"]
+    assert not [s for lib in _lib.LIBRARIES for s in lib.sources if s in ("tamf_f32_tower.h", "tamf_weights.h")]
+    assert not [s for s in _lib.TEXTENC.sources if s.startswith("tamf_pointenc")] and not [s for s in _lib.POINTENC.sources if s.startswith("tamf_textenc")]
     assert not [s for lib in _lib.LIBRARIES + _lib.PREPROCESSING for s in lib.sources if s.startswith("tamf_textenc")]
     assert _lib.LIBRARIES == (_lib.SAMPLER, _lib.EVAL, _lib.MANO) and _lib.PREPROCESSING == (_lib.POINTENC,) and _lib.TEXT_PREPROCESSING == (_lib.TEXTENC,)
     assert _lib.TEXTENC.paths == [_lib.TEXTENC_LIB_PATH] and len(_lib.EXPORTS) == 27
