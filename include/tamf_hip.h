@@ -195,14 +195,19 @@ int tamf_pose_decode(const float* pose_repr_dev, int64_t n_frames, int32_t n_joi
  * model/loss/chamfer_distance.py:4-64 with y_normals = None; replaces the external chamfer_distance CUDA extension):
  *   h2o[b,t,v] = min_{o < obj_num[b], j < P} || hand_verts[b,t,v] - (R(b,o,t) obj_points[b,o,j] + tsl(b,o,t)) ||_2
  * hand_verts (B,T,V,3), obj_traj (B,nobj,T,9) = [tsl | rot6d], obj_points (B,nobj,P,3) in the object frame,
- * obj_num (B,) int32 device or NULL (= nobj for every clip), out (B,T,V); V <= 1024. */
+ * obj_num (B,) int32 device or NULL (= nobj for every clip), out (B,T,V); V <= 1024, B <= 65535.
+ * Contract on the device-side counts: every obj_num[b] is in [1, nobj].  The entry point cannot read them without a
+ * synchronisation and does not: the caller checks them where it still has them on the host (oakink2_tamf_amd.geometry raises
+ * ValueError).  Outside the contract the kernel stays inside its buffers but the values mean nothing: a count above nobj is
+ * taken as nobj, a count <= 0 leaves no point to measure against and every distance of the clip is sqrt(3e38) = 1.7e19.
+ * Objects o >= obj_num[b] of a clip are never read (they may hold anything, NaN included). */
 int tamf_h2o_dist(const float* hand_verts_dev, const float* obj_traj_dev, const float* obj_points_dev,
                   const int32_t* obj_num_dev, int32_t B, int32_t T, int32_t V, int32_t nobj, int32_t P,
                   float* h2o_out_dev, void* stream);
 /* Per-frame contact distance of the Contact-Ratio score (script/compute_score/compute_score_cr.py:122-149,282-283:
  * transf_merge_obj_pointcloud + torch.cdist(hand_verts, merged_points).min per frame; a frame is "in contact" when
- * the value is < 0.005 m):  min_dist[b,t] = min_v h2o[b,t,v] with h2o as in tamf_h2o_dist.  Same argument layout;
- * min_dist_out (B,T). */
+ * the value is < 0.005 m):  min_dist[b,t] = min_v h2o[b,t,v] with h2o as in tamf_h2o_dist, bit for bit.  Same argument
+ * layout, same limits and the same contract on obj_num; min_dist_out (B,T). */
 int tamf_contact_min_dist(const float* hand_verts_dev, const float* obj_traj_dev, const float* obj_points_dev,
                           const int32_t* obj_num_dev, int32_t B, int32_t T, int32_t V, int32_t nobj, int32_t P,
                           float* min_dist_out_dev, void* stream);

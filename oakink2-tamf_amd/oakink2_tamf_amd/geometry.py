@@ -64,8 +64,12 @@ def _h2o_call(entry: str, hand_verts, obj_traj, obj_points, obj_num, per_vertex:
     assert tuple(tr.shape) == (B, nobj, T, 9) and pts.shape[0] == B and pts.shape[3] == 3
     on = None
     if obj_num is not None:
-        on = torch.as_tensor(list(obj_num), dtype=torch.int32, device=dev)
-        assert on.numel() == B
+        counts = [int(n) for n in obj_num]
+        assert len(counts) == B
+        for b, n in enumerate(counts):  # the kernel cannot refuse: it would clamp a count above nobj and return 1.7e19 for one <= 0
+            if not 1 <= n <= nobj:
+                raise ValueError(f"{entry}: obj_num[{b}] = {n} of clip {b} is outside [1, nobj = {nobj}]")
+        on = torch.as_tensor(counts, dtype=torch.int32, device=dev)
     out = torch.empty((B, T, V) if per_vertex else (B, T), device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
         _check(getattr(_bind(), entry)(c_void_p(hv.data_ptr()), c_void_p(tr.data_ptr()), c_void_p(pts.data_ptr()),
