@@ -1,0 +1,441 @@
+// SegmentEncoder training step (libtamf_enctrain.so): the training-mode forward, the cross-entropy loss and the gradient of every
+// parameter, fp32 throughout.  Every linear map - forward, data gradient and weight gradient - runs on v_mfma_f32_16x16x4_f32 through
+// two kernels (lin_kernel: token rows are the M dimension; wgrad_kernel: token rows are the reduction dimension).  The weights are
+// read where torch keeps them, in state-dict layout ([out][in] row-major), the gradients are written where torch's .grad live.
+//
+// Determinism.  No floating-point atomics.  Every output element is one thread's sum in a fixed order: a forward value depends on
+// its own clip only (clip b's activation has the same bits alone and in any batch), a weight gradient is the sum of per-split partial
+// sums (rows split by a function of the row count alone) added in split order by reduce_kernel.
+//
+// Dropout.  keep(seed, step, clip, site, element) is word (element & 3) of Philox4x32-10 block (element >> 2, step, clip_lo, clip_hi)
+// under key (seed_lo ^ site * 0x9E3779B1, seed_hi), compared against p * 2^32; kept values are scaled by 1 / (1 - p).  The backward
+// regenerates the masks; none is stored.  At p = 0 the threshold is 0 (everything kept, the draw skipped) and the scale is exactly 1: the
+// same kernels and the bits of a call whose draws all keep (tested at p = 2^-32), which are the bits of no dropout.
+//   site 0               x + PE                   element = row * 64 + col          (row: token row of the clip, 0 .. S-1)
+//   site 1 + 4 l         attention probabilities  element = (head * S + query) * S + key
+//   site 2 + 4 l         out-projection output    element = row * 64 + col
+//   site 3 + 4 l         GELU output              element = row * ff + col
+//   site 4 + 4 l         linear2 output           element = row * 64 + col
+#pragma once
+#include "tamf_encoder.h"
+
+constexpr int EG_H = ENC_D / ENC_HD;  // heads
+constexpr int EG_MAX_S = 512;         // token rows of a clip: K_h | V_h (or Q_h | dO_h) of one head in 64 KiB of LDS
+
+// rows of a (clips x rows-per-clip) selection inside a [B][S][ld] buffer: row m lives at (m / G) * gs + (m % G) * ld floats
+struct RowMap {
+  int G;
+  long gs, ld;
+  TAMF_DEV long at(int m) const { return (long)(m / G) * gs + (long)(m % G) * ld; }
+};
+
+struct Drop {
+  uint32_t k0, k1, step, thr;  // key, step, keep threshold (keep when the draw >= thr)
+  float scale;                 // 1 / (1 - p)
+  const long long* clip;       // [B] clip ids or null (b)
+};
+TAMF_DEV uint32_t drop_key0(const Drop& d, int site) { return d.k0 ^ ((uint32_t)site * 0x9E3779B1u); }
+TAMF_DEV bool drop_keep_id(const Drop& d, int site, unsigned long long c, uint32_t e) {
+  if (d.thr == 0) return true;
+  uint32_t r[4];
+  philox4x32_10(e >> 2, d.step, (uint32_t)(c & 0xFFFFFFFFu), (uint32_t)(c >> 32), drop_key0(d, site), d.k1, r);
+  const uint32_t v = (e & 3) == 0 ? r[0] : (e & 3) == 1 ? r[1] : (e & 3) == 2 ? r[2] : r[3];
+  return v >= d.thr;
+}
+TAMF_DEV bool drop_keep(const Drop& d, int site, int b, uint32_t e) {
+  if (d.thr == 0) return true;
+  return drop_keep_id(d, site, d.clip ? (unsigned long long)d.clip[b] : (unsigned long long)b, e);
+}
+// the factor of a dropped-out value: 0 or 1 / (1 - p)
+TAMF_DEV float drop_factor(const Drop& d, int site, int b, uint32_t e) { return drop_keep(d, site, b, e) ? d.scale : 0.f; }
+
+TAMF_DEV float silu_grad(float x) {
+  const float s = 1.0f / (1.0f + expf(-x));
+  return s * (1.0f + x * (1.0f - s));
+}
+TAMF_DEV float gelu_grad(float x) {
+  return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.3989422804014327f * expf(-0.5f * x * x);
+}
+
+enum EgMode {
+  EG_LIN = 0,        // C = v
+  EG_SILU,           // C2 = v, C = silu(v)
+  EG_GELU_DROP,      // C2 = v, C = drop(gelu(v))
+  EG_DROP_RES,       // C = R + drop(v)
+  EG_BWD_SILU,       // C = v * silu'(R)
+  EG_BWD_GELU_DROP,  // C = v * drop factor * gelu'(R)
+  EG_BWD_RES,        // C = v + R
+  EG_BWD_RES_Q0,     // C = v + (row of the clip >= q0 ? R : 0)
+};
+
+// C[m][n] = epilogue(sum_k A[am(m) + k] * W[n * swn + k * swk] + bias[n]), v = the sum with the bias.  One wave per 16 x 16 tile; a
+// lane (r = lane & 15, g = lane >> 4) feeds A row r / W column r at k + g and receives rows 4g..4g+3 of column r (as enc_gemm).
+struct LinArgs {
+  const float* A;
+  RowMap am;
+  const float* W;
+  long swn, swk;
+  const float* bias;  // [N] or null
+  float* C;
+  RowMap cm;  // also the (clip, row) split of m for the dropout element and EG_BWD_RES_Q0: b = m / cm.G, row = q0 + m % cm.G
+  float* C2;  // at cm as well
+  const float* R;
+  RowMap rm;
+  int M, N, K, mode, site, q0, rq0;  // q0: the clip row of m % cm.G = 0; rq0: EG_BWD_RES_Q0's first row with an R
+  Drop d;
+};
+__global__ __launch_bounds__(256) void lin_kernel(const LinArgs a) {
+  const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+  const int nt = (a.N + 15) >> 4, mt = (a.M + 15) >> 4;
+  const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= (long)mt * nt) return;
+  const int m0 = (int)(t / nt) << 4, n0 = (int)(t % nt) << 4;
+  const bool arow = m0 + r < a.M, wcol = n0 + r < a.N;
+  const float* ap = a.A + (arow ? a.am.at(m0 + r) : 0);
+  const float* wp = a.W + (wcol ? (long)(n0 + r) * a.swn : 0);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int k = g; k < a.K + g; k += 4) {  // (every lane of the wave makes the same number of trips: k - g < K)
+    const bool in = k < a.K;
+    const float av = arow && in ? ap[k] : 0.f;
+    const float wv = wcol && in ? wp[(long)k * a.swk] : 0.f;
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, wv, acc, 0, 0, 0);
+  }
+  const int n = n0 + r;
+  if (n >= a.N) return;
+  const float bias = a.bias ? a.bias[n] : 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + 4 * g + i;
+    if (m >= a.M) continue;
+    const float v = acc[i] + bias;
+    const int b = m / a.cm.G, row = a.q0 + m % a.cm.G;
+    const long co = a.cm.at(m) + n;
+    float o = v;
+    switch (a.mode) {
+      case EG_LIN: break;
+      case EG_SILU:
+        a.C2[co] = v;
+        o = silu_exact(v);
+        break;
+      case EG_GELU_DROP:
+        a.C2[co] = v;
+        o = gelu_erf(v) * drop_factor(a.d, a.site, b, (uint32_t)row * a.N + n);
+        break;
+      case EG_DROP_RES: o = a.R[a.rm.at(m) + n] + v * drop_factor(a.d, a.site, b, (uint32_t)row * a.N + n); break;
+      case EG_BWD_SILU: o = v * silu_grad(a.R[a.rm.at(m) + n]); break;
+      case EG_BWD_GELU_DROP: o = v * drop_factor(a.d, a.site, b, (uint32_t)row * a.N + n) * gelu_grad(a.R[a.rm.at(m) + n]); break;
+      case EG_BWD_RES: o = v + a.R[a.rm.at(m) + n]; break;
+      case EG_BWD_RES_Q0: o = row >= a.rq0 ? v + a.R[a.rm.at(m) + n] : v; break;
+    }
+    a.C[co] = o;
+  }
+}
+
+// part[s][n][k] = sum over the rows r of split s of Y[ym(r) + n] * A[am(r) + k], k < K; column k = K is the sum of Y itself (the bias
+// gradient).  One wave per (16 x 16 tile, split); rows are the MFMA's reduction dimension.
+struct WgradArgs {
+  const float* Y;
+  RowMap ym;
+  const float* A;
+  RowMap am;
+  float* part;  // [nsplit][N][K + 1]
+  int R, N, K, nsplit, chunk;  // chunk: rows per split, a multiple of 4
+};
+__global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
+  const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+  const int K1 = a.K + 1, nt = (a.N + 15) >> 4, kt = (K1 + 15) >> 4;
+  const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= (long)nt * kt * a.nsplit) return;
+  const int s = (int)(t / ((long)nt * kt)), tt = (int)(t % ((long)nt * kt));
+  const int n0 = (tt / kt) << 4, k0 = (tt % kt) << 4;
+  const int n = n0 + r, k = k0 + r;
+  const int r0 = s * a.chunk, r1 = min(a.R, r0 + a.chunk);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int q = r0 + g; q < r1 + g; q += 4) {
+    const bool in = q < r1;
+    const float yv = in && n < a.N ? a.Y[a.ym.at(q) + n] : 0.f;
+    const float av = !in ? 0.f : k < a.K ? a.A[a.am.at(q) + k] : k == a.K ? 1.0f : 0.f;
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(yv, av, acc, 0, 0, 0);
+  }
+  if (k >= K1) return;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int nn = n0 + 4 * g + i;
+    if (nn < a.N) a.part[((long)s * a.N + nn) * K1 + k] = acc[i];
+  }
+}
+// dW[n][k] (k < K) and db[n] (k = K, K1 = K + 1) = the partial sums added in split order; K1 = K: no bias column
+__global__ void reduce_kernel(const float* part, int nsplit, int N, int K1, int K, float* dW, float* db) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x, tot = (long)N * K1;
+  if (e >= tot) return;
+  float s = 0.f;
+  for (int i = 0; i < nsplit; ++i) s += part[(long)i * tot + e];
+  const int n = (int)(e / K1), k = (int)(e % K1);
+  if (k < K) dW[(long)n * K + k] = s;
+  else db[n] = s;
+}
+// part[s][c] = sum over the rows of split s of X[xm(r) + c], c < 64 (LayerNorm gain / bias gradients); block = 64 threads
+__global__ void colsum_kernel(const float* X, RowMap xm, int R, int chunk, float* part) {
+  const int s = blockIdx.x, c = threadIdx.x;
+  float v = 0.f;
+  for (int r = s * chunk; r < min(R, (s + 1) * chunk); ++r) v += X[xm.at(r) + c];
+  part[(long)s * ENC_D + c] = v;
+}
+
+// LayerNorm of 64-wide rows, one wave per row (enc_ln_row's arithmetic): Y[ym(m)] = LN(X[xm(m)])
+__global__ __launch_bounds__(256) void ln_fwd_kernel(const float* X, RowMap xm, float* Y, RowMap ym, const float* g, const float* b, int M) {
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (m >= M) return;
+  const float v = X[xm.at(m) + lane];
+  const float mean = wave_sum(v) * (1.0f / ENC_D);
+  const float dv = v - mean;
+  const float var = wave_sum(dv * dv) * (1.0f / ENC_D);
+  Y[ym.at(m) + lane] = dv * (1.0f / sqrtf(var + 1e-5f)) * g[lane] + b[lane];
+}
+// its backward, the statistics recomputed from the pre-LayerNorm row: dz = d(pre), dym = dz * the dropout factor of `site` (the
+// gradient of the linear output that was dropped out and added to the residual), tt = dy * xhat (summed over rows: the gain gradient)
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const float* DY, const float* PRE, RowMap rm, const float* g, float* DZ, float* DYM,
+                                                     float* TT, int M, int q0, int site, Drop d) {
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (m >= M) return;
+  const long o = rm.at(m) + lane;
+  const float v = PRE[o];
+  const float mean = wave_sum(v) * (1.0f / ENC_D);
+  const float dv = v - mean;
+  const float var = wave_sum(dv * dv) * (1.0f / ENC_D);
+  const float rstd = 1.0f / sqrtf(var + 1e-5f), xhat = dv * rstd;
+  const float dy = DY[o], gy = dy * g[lane];
+  const float m1 = wave_sum(gy) * (1.0f / ENC_D), m2 = wave_sum(gy * xhat) * (1.0f / ENC_D);
+  const float dz = rstd * (gy - m1 - xhat * m2);
+  DZ[o] = dz;
+  DYM[o] = dz * drop_factor(d, site, m / rm.G, (uint32_t)(q0 + m % rm.G) * ENC_D + lane);
+  TT[o] = dy * xhat;
+}
+
+// ---- attention, one thread per query (forward, dQ) or per key (dK, dV); QKV rows are [q(64) | k(64) | v(64)], head h at 16 h ----
+struct AttnArgs {
+  const float* qkv;  // [B][S][192]
+  float* att;        // [B][S][64]   forward: out
+  float* stat;       // [B][H][S][2] (max, sum) of the scaled scores
+  const float* datt; // [B][S][64]
+  float* dqkv;       // [B][S][192]
+  float* delta;      // [B][H][S]
+  int S, q0, site;
+  Drop d;
+};
+__global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnArgs a) {
+  extern __shared__ float eg_lds[];
+  const int S = a.S, h = blockIdx.y, b = blockIdx.z, HD = ENC_HD;
+  float* Kh = eg_lds;
+  float* Vh = eg_lds + (long)S * HD;
+  const float* base = a.qkv + (long)b * S * 192;
+  for (int e = threadIdx.x; e < S * HD; e += 64) {
+    const int k = e / HD, j = e % HD;
+    Kh[e] = base[(long)k * 192 + 64 + h * HD + j];
+    Vh[e] = base[(long)k * 192 + 128 + h * HD + j];
+  }
+  __syncthreads();
+  const int q = a.q0 + blockIdx.x * 64 + threadIdx.x;
+  if (q >= S) return;
+  const float scale = 1.0f / sqrtf((float)HD);
+  float qv[ENC_HD], o[ENC_HD];
+#pragma unroll
+  for (int j = 0; j < HD; ++j) { qv[j] = base[(long)q * 192 + h * HD + j]; o[j] = 0.f; }
+  float mx = -__builtin_inff();
+  for (int k = 0; k < S; ++k) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < HD; ++j) s = fmaf(qv[j], Kh[k * HD + j], s);
+    mx = fmaxf(mx, s * scale);
+  }
+  float sum = 0.f;
+  const uint32_t e0 = (uint32_t)(h * S + q) * S;
+  for (int k = 0; k < S; ++k) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < HD; ++j) s = fmaf(qv[j], Kh[k * HD + j], s);
+    const float p = expf(s * scale - mx);
+    sum += p;
+    const float pd = p * drop_factor(a.d, a.site, b, e0 + k);
+#pragma unroll
+    for (int j = 0; j < HD; ++j) o[j] = fmaf(pd, Vh[k * HD + j], o[j]);
+  }
+  const float inv = 1.0f / sum;
+#pragma unroll
+  for (int j = 0; j < HD; ++j) a.att[((long)b * S + q) * ENC_D + h * HD + j] = o[j] * inv;
+  float* st = a.stat + (((long)b * EG_H + h) * S + q) * 2;
+  st[0] = mx;
+  st[1] = sum;
+}
+// dQ of every row (zero below q0) and delta[q] = sum_k P_qk dP_qk
+__global__ __launch_bounds__(64) void attn_bwd_q_kernel(const AttnArgs a) {
+  extern __shared__ float eg_lds[];
+  const int S = a.S, h = blockIdx.y, b = blockIdx.z, HD = ENC_HD;
+  float* Kh = eg_lds;
+  float* Vh = eg_lds + (long)S * HD;
+  const float* base = a.qkv + (long)b * S * 192;
+  for (int e = threadIdx.x; e < S * HD; e += 64) {
+    const int k = e / HD, j = e % HD;
+    Kh[e] = base[(long)k * 192 + 64 + h * HD + j];
+    Vh[e] = base[(long)k * 192 + 128 + h * HD + j];
+  }
+  __syncthreads();
+  const int q = blockIdx.x * 64 + threadIdx.x;
+  if (q >= S) return;
+  float* dq = a.dqkv + ((long)b * S + q) * 192 + h * HD;
+  if (q < a.q0) {
+#pragma unroll
+    for (int j = 0; j < HD; ++j) dq[j] = 0.f;
+    return;
+  }
+  const float scale = 1.0f / sqrtf((float)HD);
+  const float* st = a.stat + (((long)b * EG_H + h) * S + q) * 2;
+  const float mx = st[0], inv = 1.0f / st[1];
+  float qv[ENC_HD], dO[ENC_HD], acc[ENC_HD];
+#pragma unroll
+  for (int j = 0; j < HD; ++j) {
+    qv[j] = base[(long)q * 192 + h * HD + j];
+    dO[j] = a.datt[((long)b * S + q) * ENC_D + h * HD + j];
+    acc[j] = 0.f;
+  }
+  const uint32_t e0 = (uint32_t)(h * S + q) * S;
+  float delta = 0.f;
+  for (int k = 0; k < S; ++k) {
+    float s = 0.f, dp = 0.f;
+#pragma unroll
+    for (int j = 0; j < HD; ++j) { s = fmaf(qv[j], Kh[k * HD + j], s); dp = fmaf(dO[j], Vh[k * HD + j], dp); }
+    const float p = expf(s * scale - mx) * inv;
+    delta += p * dp * drop_factor(a.d, a.site, b, e0 + k);
+  }
+  for (int k = 0; k < S; ++k) {
+    float s = 0.f, dp = 0.f;
+#pragma unroll
+    for (int j = 0; j < HD; ++j) { s = fmaf(qv[j], Kh[k * HD + j], s); dp = fmaf(dO[j], Vh[k * HD + j], dp); }
+    const float p = expf(s * scale - mx) * inv;
+    const float ds = p * (dp * drop_factor(a.d, a.site, b, e0 + k) - delta);
+#pragma unroll
+    for (int j = 0; j < HD; ++j) acc[j] = fmaf(ds, Kh[k * HD + j], acc[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < HD; ++j) dq[j] = acc[j] * scale;
+  a.delta[((long)b * EG_H + h) * S + q] = delta;
+}
+// dK and dV of key k: the queries q0 .. S-1 in order
+__global__ __launch_bounds__(64) void attn_bwd_kv_kernel(const AttnArgs a) {
+  extern __shared__ float eg_lds[];
+  const int S = a.S, h = blockIdx.y, b = blockIdx.z, HD = ENC_HD, nq = S - a.q0;
+  float* Qh = eg_lds;                    // [nq][16]
+  float* Oh = eg_lds + (long)nq * HD;    // [nq][16] dO
+  const float* base = a.qkv + (long)b * S * 192;
+  for (int e = threadIdx.x; e < nq * HD; e += 64) {
+    const int q = a.q0 + e / HD, j = e % HD;
+    Qh[e] = base[(long)q * 192 + h * HD + j];
+    Oh[e] = a.datt[((long)b * S + q) * ENC_D + h * HD + j];
+  }
+  __syncthreads();
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= S) return;
+  const float scale = 1.0f / sqrtf((float)HD);
+  float kv[ENC_HD], vv[ENC_HD], dk[ENC_HD], dv[ENC_HD];
+#pragma unroll
+  for (int j = 0; j < HD; ++j) {
+    kv[j] = base[(long)k * 192 + 64 + h * HD + j];
+    vv[j] = base[(long)k * 192 + 128 + h * HD + j];
+    dk[j] = 0.f;
+    dv[j] = 0.f;
+  }
+  const float* st = a.stat + ((long)b * EG_H + h) * S * 2;
+  const float* dl = a.delta + ((long)b * EG_H + h) * S;
+  for (int i = 0; i < nq; ++i) {
+    const int q = a.q0 + i;
+    float s = 0.f, dp = 0.f;
+#pragma unroll
+    for (int j = 0; j < HD; ++j) { s = fmaf(Qh[i * HD + j], kv[j], s); dp = fmaf(Oh[i * HD + j], vv[j], dp); }
+    const float p = expf(s * scale - st[2 * q]) / st[2 * q + 1];
+    const float f = drop_factor(a.d, a.site, b, (uint32_t)(h * S + q) * S + k);
+    const float ds = p * (dp * f - dl[q]) * scale, pd = p * f;
+#pragma unroll
+    for (int j = 0; j < HD; ++j) { dk[j] = fmaf(ds, Qh[i * HD + j], dk[j]); dv[j] = fmaf(pd, Oh[i * HD + j], dv[j]); }
+  }
+  float* o = a.dqkv + ((long)b * S + k) * 192 + h * HD;
+#pragma unroll
+  for (int j = 0; j < HD; ++j) { o[64 + j] = dk[j]; o[128 + j] = dv[j]; }
+}
+
+// ---- input stage ----
+struct PrepArgs {
+  const float *shape, *oemb, *traj;  // (B,T,sd) (B,nobj,od) (B,nobj,T,qd)
+  const unsigned char* side;                // [B] 0 = rh, 1 = lh
+  const int* cnt;                           // [B] or null
+  const float *rh, *lh, *cls;               // [64] each
+  float *shm, *oem, *trm, *pre;             // [B][sd] [B][od] [B*T][qd]; pre [B][S][64]: rows 0 and S-1 are written here
+  int B, T, nobj, sd, od, qd;
+};
+__global__ void prep_kernel(const PrepArgs a) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int S = a.T + ENC_P + 1;
+  const long n0 = (long)a.B * a.sd, n1 = n0 + (long)a.B * a.od, n2 = n1 + (long)a.B * a.T * a.qd, n3 = n2 + (long)a.B * 2 * ENC_D;
+  if (e < n0) {
+    const int b = (int)(e / a.sd), c = (int)(e % a.sd);
+    double s = 0.0;  // (T terms of one sign: a float32 running sum would lose log2(T) bits of the hand-shape row)
+    for (int t = 0; t < a.T; ++t) s += (double)a.shape[((long)b * a.T + t) * a.sd + c];
+    a.shm[e] = (float)(s / (double)a.T);
+  } else if (e < n1) {
+    const long i = e - n0;
+    const int b = (int)(i / a.od), c = (int)(i % a.od);
+    const int n = a.cnt ? max(1, min(a.cnt[b], a.nobj)) : a.nobj;
+    float s = 0.f;
+    for (int o = 0; o < n; ++o) s += a.oemb[((long)b * a.nobj + o) * a.od + c];
+    a.oem[i] = s / (float)n;
+  } else if (e < n2) {
+    const long i = e - n1;
+    const int c = (int)(i % a.qd);
+    const long bt = i / a.qd;
+    const int b = (int)(bt / a.T), t = (int)(bt % a.T);
+    const int n = a.cnt ? max(1, min(a.cnt[b], a.nobj)) : a.nobj;
+    float s = 0.f;
+    for (int o = 0; o < n; ++o) s += a.traj[(((long)b * a.nobj + o) * a.T + t) * a.qd + c];
+    a.trm[i] = s / (float)n;
+  } else if (e < n3) {
+    const long i = e - n2;
+    const int b = (int)(i / (2 * ENC_D)), c = (int)(i % (2 * ENC_D));
+    if (c < ENC_D) a.pre[(long)b * S * ENC_D + c] = (a.side[b] ? a.lh : a.rh)[c];
+    else a.pre[((long)b * S + S - 1) * ENC_D + c - ENC_D] = a.cls[c - ENC_D];
+  }
+}
+// X0 = drop(nan_to_num(pre) + PE) over [B][S][64]; its backward: dpre = dX0 * drop factor * isfinite(pre)
+__global__ void assemble_kernel(const float* pre, const float* pe, float* x0, const float* dx0, float* dpre, int B, int S, Drop d) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)B * S * ENC_D) return;
+  const int b = (int)(e / ((long)S * ENC_D));
+  const uint32_t el = (uint32_t)(e % ((long)S * ENC_D));
+  const float f = drop_factor(d, 0, b, el), v = pre[e];
+  if (x0) x0[e] = (nan_to_num(v) + pe[el]) * f;
+  else dpre[e] = (v - v == 0.f) ? dx0[e] * f : 0.f;  // (v - v: 0 for a finite v, NaN otherwise)
+}
+
+// loss = mean_b CE(act[b], label[b]); dact = (softmax - onehot) / B.  One block; the per-clip losses are added in clip order.
+__global__ __launch_bounds__(256) void ce_kernel(const float* act, const long long* label, int B, int F, float* lb, float* dact, float* loss) {
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const float* x = act + (long)b * F;
+    float mx = -__builtin_inff();
+    for (int c = 0; c < F; ++c) mx = fmaxf(mx, x[c]);
+    float s = 0.f;
+    for (int c = 0; c < F; ++c) s += expf(x[c] - mx);
+    const int y = (int)min(max(label[b], 0LL), (long long)(F - 1));  // (the caller checks the range; never read outside the row)
+    lb[b] = logf(s) + mx - x[y];
+    const float inv = 1.0f / (s * (float)B);
+    for (int c = 0; c < F; ++c) dact[(long)b * F + c] = expf(x[c] - mx) * inv - (c == y ? 1.0f / (float)B : 0.f);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) s += lb[b];
+    *loss = s / (float)B;
+  }
+}
+
+__global__ void dropout_mask_kernel(Drop d, int site, unsigned long long clip, long n, unsigned char* out) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) out[e] = drop_keep_id(d, site, clip, (uint32_t)e) ? 1 : 0;
+}

@@ -8,6 +8,7 @@ that description:
   MANO     csrc/tamf_mano.hip -> libtamf_mano.so (include/tamf_mano.h: the native MANO hand layer)
   POINTENC csrc/tamf_pointenc.hip -> libtamf_pointenc.so (include/tamf_pointenc.h: the PointBERT point encoder behind obj_embedding)
   TEXTENC  csrc/tamf_textenc.hip -> libtamf_textenc.so (include/tamf_textenc.h: the CLIP text tower behind text_embedding)
+  ENCTRAIN csrc/tamf_enctrain.hip -> libtamf_enctrain.so (include/tamf_enctrain.h: the SegmentEncoder training step - forward, loss, gradients)
 POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
 score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
 Every library has its own sources, stamp and lock: building or loading one never touches another."""
@@ -31,6 +32,7 @@ EVAL_LIB_PATH = os.path.join(LIB_DIR, "libtamf_eval.so")
 MANO_LIB_PATH = os.path.join(LIB_DIR, "libtamf_mano.so")
 POINTENC_LIB_PATH = os.path.join(LIB_DIR, "libtamf_pointenc.so")
 TEXTENC_LIB_PATH = os.path.join(LIB_DIR, "libtamf_textenc.so")
+ENCTRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_enctrain.so")
 
 EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_ctx_create", "tamf_ctx_resize", "tamf_ctx_destroy", "tamf_last_error", "tamf_load_weight", "tamf_finalize_weights",
@@ -57,6 +59,10 @@ POINTENC_EXPORTS = [  # include/tamf_pointenc.h: what libtamf_pointenc.so export
 TEXTENC_EXPORTS = [  # include/tamf_textenc.h: what libtamf_textenc.so exports
     "tamf_textenc_last_error", "tamf_textenc_model_create", "tamf_textenc_load_weight", "tamf_textenc_finalize", "tamf_textenc_destroy",
     "tamf_textenc_workspace_bytes", "tamf_textenc_encode",
+]
+ENCTRAIN_EXPORTS = [  # include/tamf_enctrain.h: what libtamf_enctrain.so exports
+    "tamf_enctrain_last_error", "tamf_enctrain_create", "tamf_enctrain_destroy", "tamf_enctrain_bind", "tamf_enctrain_step",
+    "tamf_enctrain_dropout_mask",
 ]
 
 
@@ -255,14 +261,18 @@ POINTENC = Library("libtamf_pointenc", "tamf_pointenc.hip", ("tamf_pointenc.h", 
 TEXTENC = Library("libtamf_textenc", "tamf_textenc.hip", ("tamf_textenc.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
                   (Output("libtamf_textenc.so", (), TEXTENC_EXPORTS),),
                   kernels=("_Z12embed_kernel", "_Z9ln_kernel", "_Z15f32_gemm_kernelI5TeEpiE", "_Z11attn_kernel"))
+ENCTRAIN = Library("libtamf_enctrain", "tamf_enctrain.hip", ("tamf_enctrain.h", "tamf_hip.h"),  # (tamf_hip.h for tamf_status and tamf_arch)
+                   (Output("libtamf_enctrain.so", (), ENCTRAIN_EXPORTS),),
+                   kernels=("_Z10lin_kernel", "_Z12wgrad_kernel", "_Z15attn_fwd_kernel", "_Z17attn_bwd_q_kernel", "_Z18attn_bwd_kv_kernel"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)
+TRAINING = (ENCTRAIN,)  # the SegmentEncoder training step (launch/train_encoder.py)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Every library, the sampler pair first, each only when ITS sources changed.  One library at a time.  Returns LIB_PATH."""
-    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING:
+    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING:
         lib.build(force, verbose)
     return LIB_PATH
 
@@ -319,6 +329,11 @@ def load_pointenc() -> ctypes.CDLL:
 def load_textenc() -> ctypes.CDLL:
     """libtamf_textenc.so (include/tamf_textenc.h).  Independent of the other libraries."""
     return _load(TEXTENC, "libtamf_textenc.so")
+
+
+def load_enctrain() -> ctypes.CDLL:
+    """libtamf_enctrain.so (include/tamf_enctrain.h).  Independent of the other libraries."""
+    return _load(ENCTRAIN, "libtamf_enctrain.so")
 
 
 def load_from(path: str) -> ctypes.CDLL:

@@ -8,7 +8,10 @@
     sample_info       (basename of the directory, sample_id)
     sample_pose_repr  the array of the i-th .npy file, files taken directory by directory in sorted name order
 
-The join is positional: the number of .npy files must equal the number of dataset items (the reference asserts it)."""
+The join is positional: the number of .npy files must equal the number of dataset items (the reference asserts it).
+
+`GuassianPerturbSampleAdaptor` (the reference's spelling, :55-94) is the third part of the encoder's training set: the item's own pose
+with Gaussian noise on its valid frames, the rot6d halves renormalised."""
 from __future__ import annotations
 
 import os
@@ -48,6 +51,37 @@ class GeneratedPoseReprSampleAdaptor:
 
     def __len__(self) -> int:
         return self.len
+
+
+class GuassianPerturbSampleAdaptor:
+    """item i with a noisy copy of its pose as the "sample": sigma ~ U(sigma_range); on the item's first `len` frames the translation
+    (columns 0:3) gets N(0, 0.1 sigma) and the 16 rot6d poses (columns 3:99) get N(0, sigma), then each 3-vector half of every rot6d
+    is scaled back to unit length (norms clamped at 1e-7).  Frames past `len` are untouched.  np.random is called as the reference
+    calls it - uniform, normal (len, 3), normal (len, 96) - so a seeded run draws the same noise.
+    sample_info = (index, sigma)."""
+
+    def __init__(self, interaction_segment_dataset, sigma_range: Sequence[float]):
+        self.interaction_segment_dataset = interaction_segment_dataset
+        self.sigma_min, self.sigma_max = float(sigma_range[0]), float(sigma_range[1])
+
+    def __getitem__(self, index: int) -> Dict:
+        item = self.interaction_segment_dataset[index]
+        n = int(item["len"])
+        sigma = np.random.uniform(self.sigma_min, self.sigma_max)
+        d_tsl = np.random.normal(0, 0.1 * sigma, size=(n, 3))
+        d_rot = np.random.normal(0, sigma, size=(n, 96))
+        out = item["pose_repr"].copy()
+        out[:n, 0:3] += d_tsl
+        out[:n, 3:99] += d_rot
+        halves = out[:n, 3:99].reshape(n, 32, 3)  # 16 joints x (first, second) column of the rotation
+        halves = halves / np.maximum(np.linalg.norm(halves, axis=-1, keepdims=True), 1e-7)
+        out[:n, 3:99] = halves.reshape(n, 96)
+        item["sample_info"] = (index, sigma)
+        item["sample_pose_repr"] = out
+        return item
+
+    def __len__(self) -> int:
+        return len(self.interaction_segment_dataset)
 
 
 class IdentitySampleAdaptor:
