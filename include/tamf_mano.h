@@ -1,6 +1,6 @@
 /*
  * tamf_mano.h - C-ABI of the native MANO hand layer (libtamf_mano.so): forward kinematics + linear blend skinning of the MANO hand
- * model on the GPU, from model arrays the CALLER supplies.  The MANO assets are licence-gated and are not part of this package;
+ * model on the GPU, and their backward, from model arrays the CALLER supplies.  The MANO assets are licence-gated and are not part of this package;
  * nothing here reads a file.
  *
  * What is implemented is the published definition, not a port of a particular code base:
@@ -53,7 +53,7 @@ int tamf_mano_model_create(int32_t V, const double* v_template, const double* sh
                            const double* J_regressor, const double* weights, const int32_t* parents, const int32_t* tip_ids,
                            const int32_t* joint_order, int32_t center_idx, tamf_mano_model** model_out);
 
-/* frees the device arrays (NULL is accepted); work enqueued by tamf_mano_forward must have finished */
+/* frees the device arrays (NULL is accepted); work enqueued by tamf_mano_forward / tamf_mano_backward must have finished */
 int tamf_mano_model_destroy(tamf_mano_model* model);
 
 /* Tuning only: 16-frame tiles a workgroup keeps per basis fragment (1, 2 or 4; 0 = the built-in choice).  No output bit depends on it. */
@@ -67,6 +67,20 @@ int tamf_mano_model_set_tiles(tamf_mano_model* model, int32_t m_tiles);
  * a null pointer is TAMF_ERR_INVALID.  Does not synchronise. */
 int tamf_mano_forward(const tamf_mano_model* model, const float* quat_dev, const float* betas_dev, int64_t N, float* verts_out_dev,
                       float* joints_out_dev, void* stream);
+
+/* The layer's backward: the vector-Jacobian product of exactly the function tamf_mano_forward computes, enqueued on `stream`.
+ *   quat, betas: the forward's inputs (quat 16-byte aligned); nothing is kept from a forward call, what is needed is recomputed
+ *   dverts (N,V,3) f32 device or NULL, djoints (N,21,3) f32 device or NULL: the upstream gradients of verts_out / joints_out;
+ *                NULL means zeros, both NULL is TAMF_ERR_INVALID
+ *   dquat_out (N,16,4) f32 device, 16-byte aligned: with respect to the input as given (the normalisation is differentiated too)
+ *   dbetas_out (N,10) f32 device, or NULL
+ * Covers the joint permutation, the fingertip rows (their gradient lands on the fingertip vertices) and the centre (minus the sum of
+ * all upstream rows, on the centre joint or fingertip).  No gradients with respect to the model arrays.  Outputs are overwritten.
+ * fp32 throughout; the contractions over the vertices run on v_mfma_f32_16x16x4_f32 in partial sums of a fixed order; no atomics.
+ * A frame's gradient bits depend on its own inputs and the model only - not on N, on its position in the batch, on the launch or
+ * on tamf_mano_model_set_tiles.  N = 0 launches nothing; N < 0 or a null mandatory pointer is TAMF_ERR_INVALID.  Does not synchronise. */
+int tamf_mano_backward(const tamf_mano_model* model, const float* quat_dev, const float* betas_dev, int64_t N, const float* dverts_dev,
+                       const float* djoints_dev, float* dquat_out_dev, float* dbetas_out_dev, void* stream);
 
 #ifdef __cplusplus
 }

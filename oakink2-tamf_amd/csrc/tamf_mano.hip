@@ -186,3 +186,39 @@ extern "C" int tamf_mano_forward(const tamf_mano_model* m, const float* quat_dev
   if (e != hipSuccess) return fail(TAMF_ERR_HIP, hipGetErrorString(e));
   return 0;
 }
+
+extern "C" int tamf_mano_backward(const tamf_mano_model* m, const float* quat_dev, const float* betas_dev, int64_t N, const float* dverts_dev,
+                                  const float* djoints_dev, float* dquat_out_dev, float* dbetas_out_dev, void* stream) {
+  if (!m) return fail(TAMF_ERR_INVALID, "null argument");
+  if (N < 0) return fail(TAMF_ERR_INVALID, "N = " + std::to_string(N) + " is negative");
+  if (N == 0) return 0;
+  if (!quat_dev || !betas_dev || !dquat_out_dev) return fail(TAMF_ERR_INVALID, "null argument");
+  if (!dverts_dev && !djoints_dev) return fail(TAMF_ERR_INVALID, "no upstream gradient: dverts and djoints are both null");
+  if (((uintptr_t)quat_dev | (uintptr_t)dquat_out_dev) & 15) return fail(TAMF_ERR_INVALID, "quat and dquat_out must be 16-byte aligned");
+  if (N > (1LL << 31) - 64) return fail(TAMF_ERR_INVALID, "N too large for one call: split the batch");
+  ManoGradArgs ga;
+  ManoArgs& a = ga.f;
+  a.basis = m->f32;
+  a.vt = m->f32 + m->off_vt;
+  a.w = m->f32 + m->off_w;
+  a.jt = m->f32 + m->off_jt;
+  a.jd = m->f32 + m->off_jd;
+  a.tab = m->tab;
+  a.quat = quat_dev;
+  a.betas = betas_dev;
+  a.verts = nullptr;
+  a.joints = nullptr;
+  a.N = (int)N, a.V = m->V, a.Vp = m->Vp, a.center = m->center, a.maxdepth = m->maxdepth, a.tiles_per_group = 0;
+  ga.dverts = dverts_dev;
+  ga.djoints = djoints_dev;
+  ga.dquat = dquat_out_dev;
+  ga.dbetas = dbetas_out_dev;
+  // one workgroup per 16 frames, whatever m_tiles says: the launch enters no operation's operands or order
+  const size_t lds = (size_t)MANO_GL_FLOATS * sizeof(float);
+  hipError_t e = hipFuncSetAttribute((const void*)mano_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return fail(TAMF_ERR_HIP, hipGetErrorString(e));
+  hipLaunchKernelGGL(mano_backward_kernel, dim3((unsigned)((N + 15) / 16)), dim3(MANO_NT), lds, (hipStream_t)stream, ga);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail(TAMF_ERR_HIP, hipGetErrorString(e));
+  return 0;
+}

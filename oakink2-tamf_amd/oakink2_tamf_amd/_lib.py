@@ -51,6 +51,7 @@ EVAL_EXPORTS = [  # include/tamf_eval.h: what libtamf_eval.so exports
 ]
 MANO_EXPORTS = [  # include/tamf_mano.h: what libtamf_mano.so exports
     "tamf_mano_last_error", "tamf_mano_model_create", "tamf_mano_model_destroy", "tamf_mano_model_set_tiles", "tamf_mano_forward",
+    "tamf_mano_backward",
 ]
 POINTENC_EXPORTS = [  # include/tamf_pointenc.h: what libtamf_pointenc.so exports
     "tamf_pointenc_last_error", "tamf_pointenc_model_create", "tamf_pointenc_load_weight", "tamf_pointenc_finalize", "tamf_pointenc_destroy",

@@ -14,7 +14,10 @@ source was not available.  Every convention that cannot be derived from the call
 default: the fingertip vertex ids, the 21-joint order, the centre joint.  The wrist cap of `close_wrist` is this package's own
 triangulation and may differ from manotorch's closed faces; it matters only to the SIV score's containment test near the wrist.
 
-Inference only: no autograd.
+Autograd: `HipManoLayer(..., differentiable=True)` (factory: `make_mano_differentiable`) runs the call through a
+`torch.autograd.Function` whose backward is tamf_mano_backward, the HIP vector-Jacobian product of the same function - gradients with
+respect to the quaternions (as given: the normalisation is differentiated too) and the betas, none with respect to the model arrays,
+no double backward.  The default layer stays inference only and refuses an input that requires grad.
 """
 from __future__ import annotations
 
@@ -171,6 +174,7 @@ def _bind():
         lib.tamf_mano_model_destroy.argtypes = [c_void_p]
         lib.tamf_mano_model_set_tiles.argtypes = [c_void_p, c_int32]
         lib.tamf_mano_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
+        lib.tamf_mano_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         _bound = lib
     return _bound
 
@@ -180,12 +184,48 @@ def _check(lib, rc: int) -> None:
         raise RuntimeError(f"libtamf_mano: {lib.tamf_mano_last_error().decode()} (status {rc})")
 
 
+_function = None
+
+
+def _mano_function():
+    """the torch.autograd.Function of a differentiable layer (built on first use: torch is imported lazily in this module)"""
+    global _function
+    if _function is None:
+        import torch
+
+        class ManoFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, layer, q, b, with_joints):
+                verts, joints = layer._run_forward(q, b, with_joints)
+                ctx.layer = layer
+                ctx.save_for_backward(q, b)
+                ctx.set_materialize_grads(False)  # an output nothing depends on arrives as None and is passed as NULL
+                if joints is None:
+                    return verts
+                return verts, joints
+
+            @staticmethod
+            def backward(ctx, dverts, djoints=None):
+                if torch.is_grad_enabled():  # (a backward that is itself recorded: create_graph=True)
+                    raise RuntimeError("HipManoLayer: double backward is not supported (the HIP backward is first order only; "
+                                       "call backward / autograd.grad without create_graph)")
+                if dverts is None and djoints is None:
+                    return None, None, None, None
+                q, b = ctx.saved_tensors
+                dq, db = ctx.layer.backward_raw(q, b, dverts, djoints, want_dbetas=ctx.needs_input_grad[2])
+                return None, dq if ctx.needs_input_grad[1] else None, db, None
+
+        _function = ManoFunction
+    return _function
+
+
 class HipManoLayer:
     """MANO forward on the GPU for one hand model.  `center_idx`: the OUTPUT joint subtracted from vertices and joints (0: the wrist,
     as the reference's layers are built), or None.  A missing kernel library or a device that is no GPU is an error; there is no
-    torch fall-back."""
+    torch fall-back.  `differentiable`: False (the default) is the inference layer, which refuses an input that requires grad; True
+    carries autograd through the call with the HIP backward (first order only: a double backward raises)."""
 
-    def __init__(self, arrays: ManoArrays, center_idx: Optional[int] = 0, device="cuda"):
+    def __init__(self, arrays: ManoArrays, center_idx: Optional[int] = 0, device="cuda", differentiable: bool = False):
         import torch
 
         from .hip_backend import require_gpu
@@ -196,6 +236,7 @@ class HipManoLayer:
             raise ValueError(f"center_idx = {center_idx} outside [0, {N_OUT_JOINTS})")
         self.device = require_gpu(torch.device(device))
         self.arrays, self.center_idx = arrays, None if center_idx is None else int(center_idx)
+        self.differentiable = bool(differentiable)
         self._lib = _bind()
         self._model = c_void_p()
 
@@ -234,8 +275,9 @@ class HipManoLayer:
 
         if not isinstance(pose_coeffs, torch.Tensor) or not isinstance(betas, torch.Tensor):
             raise TypeError("pose_coeffs and betas must be torch tensors")
-        if pose_coeffs.requires_grad or betas.requires_grad:
-            raise RuntimeError("HipManoLayer is inference only: an input requires grad")
+        needs_grad = torch.is_grad_enabled() and (pose_coeffs.requires_grad or betas.requires_grad)
+        if not self.differentiable and (pose_coeffs.requires_grad or betas.requires_grad):
+            raise RuntimeError("HipManoLayer is inference only: an input requires grad (build the layer with differentiable=True)")
         if pose_coeffs.dim() != 3 or tuple(pose_coeffs.shape[1:]) != (N_JOINTS, 4):
             raise ValueError(f"pose_coeffs: expected (N, 16, 4) quaternions, got {tuple(pose_coeffs.shape)}")
         N = int(pose_coeffs.shape[0])
@@ -243,16 +285,62 @@ class HipManoLayer:
             raise ValueError(f"betas: expected ({N}, {N_BETAS}), got {tuple(betas.shape)}")
         if self._model is None or not self._model.value:
             raise RuntimeError("HipManoLayer is closed")
+        if needs_grad:
+            # (the conversions stay in the graph; the Function sees float32 contiguous tensors on the layer's device)
+            q = pose_coeffs.to(device=self.device, dtype=torch.float32).contiguous()
+            b = betas.to(device=self.device, dtype=torch.float32).contiguous()
+            out = _mano_function().apply(self, q, b, bool(with_joints))
+            return ManoOutput(*out) if with_joints else ManoOutput(out, None)
         q = pose_coeffs.detach().to(device=self.device, dtype=torch.float32).contiguous()
         b = betas.detach().to(device=self.device, dtype=torch.float32).contiguous()
-        V = self.arrays.n_verts
+        return ManoOutput(*self._run_forward(q, b, with_joints))
+
+    def _run_forward(self, q, b, with_joints: bool):
+        """tamf_mano_forward on float32 contiguous device tensors -> (verts, joints or None)"""
+        import torch
+
+        from .hip_backend import _stream_ptr
+
+        N, V = int(q.shape[0]), self.arrays.n_verts
         verts = torch.empty((N, V, 3), dtype=torch.float32, device=self.device)
         joints = torch.empty((N, N_OUT_JOINTS, 3), dtype=torch.float32, device=self.device) if with_joints else None
         if N > 0:
             with torch.cuda.device(self.device):
                 _check(self._lib, self._lib.tamf_mano_forward(self._model, q.data_ptr(), b.data_ptr(), N, verts.data_ptr(),
                                                              joints.data_ptr() if with_joints else None, _stream_ptr(self.device)))
-        return ManoOutput(verts, joints)
+        return verts, joints
+
+    def backward_raw(self, pose_coeffs, betas, dverts=None, djoints=None, want_dbetas: bool = True):
+        """tamf_mano_backward: the gradients (dquat (N, 16, 4), dbetas (N, 10) or None) of the layer's outputs' upstream gradients
+        `dverts` (N, V, 3) / `djoints` (N, 21, 3) - either may be None (zeros), not both.  Recomputes what it needs from the inputs;
+        no forward call has to precede it.  N = 0 returns empty gradients without a launch."""
+        import torch
+
+        from .hip_backend import _stream_ptr
+
+        if self._model is None or not self._model.value:
+            raise RuntimeError("HipManoLayer is closed")
+        N, V = int(pose_coeffs.shape[0]), self.arrays.n_verts
+        if tuple(pose_coeffs.shape) != (N, N_JOINTS, 4) or tuple(betas.shape) != (N, N_BETAS):
+            raise ValueError(f"expected quaternions (N, 16, 4) and betas (N, 10), got {tuple(pose_coeffs.shape)} and {tuple(betas.shape)}")
+
+        def f32(t, shape, name):
+            if t is None:
+                return None
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name}: expected {shape}, got {tuple(t.shape)}")
+            return t.detach().to(device=self.device, dtype=torch.float32).contiguous()
+
+        q, b = f32(pose_coeffs, (N, N_JOINTS, 4), "pose_coeffs"), f32(betas, (N, N_BETAS), "betas")
+        dv, dj = f32(dverts, (N, V, 3), "dverts"), f32(djoints, (N, N_OUT_JOINTS, 3), "djoints")
+        dq = torch.empty((N, N_JOINTS, 4), dtype=torch.float32, device=self.device)
+        db = torch.empty((N, N_BETAS), dtype=torch.float32, device=self.device) if want_dbetas else None
+        if N > 0:
+            with torch.cuda.device(self.device):
+                _check(self._lib, self._lib.tamf_mano_backward(self._model, q.data_ptr(), b.data_ptr(), N, None if dv is None else dv.data_ptr(),
+                                                              None if dj is None else dj.data_ptr(), dq.data_ptr(),
+                                                              None if db is None else db.data_ptr(), _stream_ptr(self.device)))
+        return dq, db
 
     __call__ = forward
 
@@ -272,22 +360,31 @@ class HipManoLayer:
             pass
 
 
-def make_mano(mano_cfg, device):
-    """`--mano.factory oakink2_tamf_amd.mano:make_mano --mano.mano_path DIR`: DIR/MANO_RIGHT.npz and DIR/MANO_LEFT.npz (written by
-    tools/mano_pkl_to_npz.py) -> (layer_rh, layer_lh, closed_faces_rh, closed_faces_lh), the tuple launch/sample_refine.py:load_mano
-    documents; the layers are centred on joint 0 as the reference's are."""
+def _make_layers(mano_cfg, device, who, **layer_kw):
     d = mano_cfg.get("mano_path")
     if not d:
-        raise SystemExit("make_mano: --mano.mano_path DIR (holding MANO_RIGHT.npz and MANO_LEFT.npz) is required")
+        raise SystemExit(f"{who}: --mano.mano_path DIR (holding MANO_RIGHT.npz and MANO_LEFT.npz) is required")
     paths = [os.path.join(str(d), n) for n in ("MANO_RIGHT.npz", "MANO_LEFT.npz")]
     for p in paths:
         if not os.path.exists(p):
-            raise SystemExit(f"make_mano: {p} not found; convert your MANO_RIGHT.pkl / MANO_LEFT.pkl with tools/mano_pkl_to_npz.py "
+            raise SystemExit(f"{who}: {p} not found; convert your MANO_RIGHT.pkl / MANO_LEFT.pkl with tools/mano_pkl_to_npz.py "
                              "(the MANO assets are licence-gated and not shipped)")
     arrays = [ManoArrays.from_npz(p) for p in paths]
-    layers = [HipManoLayer(a, center_idx=0, device=device) for a in arrays]
+    layers = [HipManoLayer(a, center_idx=0, device=device, **layer_kw) for a in arrays]
     closed = [l.get_mano_closed_faces().cpu().numpy() for l in layers]
     return layers[0], layers[1], closed[0], closed[1]
 
 
-__all__ = ["ManoArrays", "HipManoLayer", "ManoOutput", "close_wrist", "make_mano", "DEFAULT_TIP_IDS", "DEFAULT_JOINT_ORDER"]
+def make_mano(mano_cfg, device):
+    """`--mano.factory oakink2_tamf_amd.mano:make_mano --mano.mano_path DIR`: DIR/MANO_RIGHT.npz and DIR/MANO_LEFT.npz (written by
+    tools/mano_pkl_to_npz.py) -> (layer_rh, layer_lh, closed_faces_rh, closed_faces_lh), the tuple launch/sample_refine.py:load_mano
+    documents; the layers are centred on joint 0 as the reference's are."""
+    return _make_layers(mano_cfg, device, "make_mano")
+
+
+def make_mano_differentiable(mano_cfg, device):
+    """make_mano with `differentiable=True` layers: what a trainer's reconstruction losses (model/reconstruction_loss.py) need"""
+    return _make_layers(mano_cfg, device, "make_mano_differentiable", differentiable=True)
+
+
+__all__ = ["ManoArrays", "HipManoLayer", "ManoOutput", "close_wrist", "make_mano", "make_mano_differentiable", "DEFAULT_TIP_IDS", "DEFAULT_JOINT_ORDER"]
