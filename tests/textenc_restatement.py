@@ -131,6 +131,20 @@ def forward(sd: Mapping[str, np.ndarray], cfg: Mapping[str, int], ids, length: O
     return x[np.arange(B), eot] @ t("text_projection")
 
 
+def layer0_scores(sd: Mapping[str, np.ndarray], cfg: Mapping[str, int], ids) -> np.ndarray:
+    """(B, H, ctx, ctx) float64: the scaled scores q . k^T * 64^-0.5 of the first block BEFORE the mask (entry [b, h, i, j]: query i
+    against key j), the same lines as `forward`'s first iteration"""
+    ids = np.asarray(ids)
+    W, H = int(cfg["width"]), int(cfg["num_heads"])
+    t = lambda k: np.asarray(sd[k]).astype(np.float64)  # noqa: E731
+    x = t("token_embedding.weight")[ids] + t("positional_embedding")[:ids.shape[1]]
+    B, T = ids.shape
+    p = "transformer.resblocks.0."
+    qkv = _layer_norm(x, t(p + "ln_1.weight"), t(p + "ln_1.bias")) @ t(p + "attn.in_proj_weight").T + t(p + "attn.in_proj_bias")
+    q, k, _ = (a.reshape(B, T, H, W // H).transpose(0, 2, 1, 3) for a in np.split(qkv, 3, axis=-1))
+    return q @ k.transpose(0, 1, 3, 2) * (W // H) ** -0.5
+
+
 def torch_tower(sd: Mapping[str, np.ndarray], cfg: Mapping[str, int], dtype, device="cpu"):
     """the model as torch.nn modules with the state dict loaded strictly: callable (B, ctx) ids -> (B, embed_dim) tensor"""
     import torch
