@@ -494,9 +494,7 @@ __global__ __launch_bounds__(attn_res_maxw(NKB_) * 64) void attn_res_kernel(cons
   // contiguous chunks (xcd_remap) - the clips whose Q | K / V^T rows the QKV GEMM's tiles on that XCD wrote last are then looked
   // up in the same L2 (aa.abl bit 5 in bench builds: plain order)
   int bh = blockIdx.y;
-#ifndef TAMF_ATTN_PLAIN_ORDER  // (A/B builds)
   if (gridDim.x == 1 && !(TAMF_ABL(aa.abl) & 32)) bh = attn_xcd_remap(bh, gridDim.y);
-#endif
   const int b = bh / aa.H, h = bh % aa.H;
   const int S = aa.S, Sp = aa.Sp, d = aa.d;
   // Key split of the clip's LAST query tile (aa.ksplit; launch_attn sets it when the clip has 4 n + 1 query tiles, e.g. 13 at T = 196).

@@ -210,23 +210,9 @@ TAMF_DEV void clip_issue(const ClipGemmArgs<Op>& ga, const ClipSrc& s, int nq, i
 // (tools/micro/issue_overlap.hip) - but priorities decide who goes first when both are ready.  The Y waves multiply at static priority 2;
 // in f32 the X waves take priority 3 for everything that is NOT their MFMA stream (fragment reads, requests, epilogue) and 0 for the
 // MFMAs: their requests are out - and their epilogue stores on the way - before the long fp32 MFMA phases of the pair begin
-// (6.50 -> 6.31 ms per step at B = 64; the 16-bit modes lose 0.2 - 0.8 % with it and keep priority 0).  -DTAMF_CLIP_XPRIO=0: off (A/B)
-#ifndef TAMF_CLIP_XPRIO
-#define TAMF_CLIP_XPRIO 1
-#endif
-#ifndef TAMF_CLIP_YFUSE  // Y waves read the next K tile's fragments inside their MFMA stream (clip_mma_read_y): bit 0 = f32, bit 1 = the 16-bit modes (A/B)
-#define TAMF_CLIP_YFUSE 1  // (f32 6.30 -> 6.235 ms per step; the 16-bit modes 0.2 - 0.8 % slower with it: profiles/r04/yfuse_c36.txt)
-#endif
-#ifndef TAMF_CLIP_SPREAD  // f32: LDS-DMA requests between the X waves' own MFMAs (clip_ktile_x; 0 = one batch ahead of them, A/B)
-#define TAMF_CLIP_SPREAD 2  // (requests behind every 8 MFMAs)
-#endif
-#if TAMF_CLIP_XPRIO
+// (6.50 -> 6.31 ms per step at B = 64; the 16-bit modes lose 0.2 - 0.8 % with it and keep priority 0).
 #define TAMF_CLIP_XPRIO_HI if constexpr (Op::PREC == 0) __builtin_amdgcn_s_setprio(3);
 #define TAMF_CLIP_XPRIO_LO if constexpr (Op::PREC == 0) __builtin_amdgcn_s_setprio(0);
-#else
-#define TAMF_CLIP_XPRIO_HI
-#define TAMF_CLIP_XPRIO_LO
-#endif
 
 // X waves, one K tile: the fragments of the first row tiles are requested, then ALL pieces of the next K tile go out into
 // `nxt`, then the MFMAs run with the A fragments streamed two row tiles ahead.  `cur` and `nxt` are the two LDS stages and
@@ -257,9 +243,10 @@ TAMF_DEV void clip_ktile_x(const char* __restrict__ cur, char* __restrict__ nxt,
   // address unit took its 16 cycles per piece and no SIMD of the CU multiplied; inside the wave's own stream a request costs an issue
   // slot and the address unit works in the shadow of the 32-cycle MFMAs.  (Early row tiles: with two stages the data is due at the
   // next barrier.)  The 16-bit modes keep the batch: their Y phase is as long as the address unit needs, and it passes requests.
-  constexpr bool SPREAD = TAMF_CLIP_SPREAD && Op::PREC == 0;
+  constexpr int SPREAD_PER = 2;  // f32: LDS-DMA requests between the X waves' own MFMAs, at least this many behind every 8 MFMAs
+  constexpr bool SPREAD = Op::PREC == 0;
   constexpr int NREQ = (C::NPIECE + 3) / 4, GROUPS = C::MSUBX * NI;  // a group = the 8 MFMAs of one (row tile, column tile) product
-  constexpr int PER = (NREQ + GROUPS - 1) / GROUPS > TAMF_CLIP_SPREAD ? (NREQ + GROUPS - 1) / GROUPS : TAMF_CLIP_SPREAD;
+  constexpr int PER = (NREQ + GROUPS - 1) / GROUPS > SPREAD_PER ? (NREQ + GROUPS - 1) / GROUPS : SPREAD_PER;
   if (load_next && !SPREAD) clip_issue<Op, C>(ga, src4, nq, prow, kt_next, nxt);
   TAMF_CLIP_XPRIO_LO
   TAMF_CLIP_TS(1)
@@ -769,7 +756,8 @@ __global__ __launch_bounds__(512, 2) void clip_gemm_kernel(const ClipGemmArgs<Op
 #endif
       TAMF_CLIP_TS(0)
       // (at 256 columns the fused form needs > 256 registers with 7 row tiles in Y: f32 gives its Y waves 6 there, tamf_hip.hip ClipXsub)
-      constexpr bool YFUSE = (NI == 2 || C::MSUBY <= 6) && (TAMF_CLIP_YFUSE & (Op::PREC == 0 ? 1 : 2)) != 0;
+      // f32 only: 6.30 -> 6.235 ms per step; the 16-bit modes are 0.2 - 0.8 % slower with it (profiles/r04/yfuse_c36.txt)
+      constexpr bool YFUSE = (NI == 2 || C::MSUBY <= 6) && Op::PREC == 0;
       if constexpr (YFUSE) clip_mma_read_y<Op, C, NI, TR>(smem + sc * C::STAGE, j < J, a_frag, w_frag, c0, c1, ywf, yaf, acc);  // K tile j - 1, fragments of K tile j
       else if (!(TAMF_ABL(ga.abl) & 2)) clip_mma_y<Op, C, NI, TR>(ywf, yaf, acc);  // K tile j - 1
 #ifdef TAMF_TIMELINE

@@ -40,10 +40,10 @@ TAMF_DEV void deep_ktile(const char* __restrict__ cur, char* __restrict__ nxt, c
 #pragma unroll
   for (int ii = 0; ii < A_PW; ++ii) {
     const int q = wave + ii * NWV;
-    if (A_PIECES % NWV == 0 || q < A_PIECES) glds16<0>(Ab + a_off[ii] + kbyte_next, nxt + q * 1024);
+    if (A_PIECES % NWV == 0 || q < A_PIECES) glds16(Ab + a_off[ii] + kbyte_next, nxt + q * 1024);
   }
 #pragma unroll
-  for (int ii = 0; ii < W_PW; ++ii) glds16<0>(Wb + w_off[ii] + kbyte_next, nxt + A_BYTES + (wave + ii * NWV) * 1024);
+  for (int ii = 0; ii < W_PW; ++ii) glds16(Wb + w_off[ii] + kbyte_next, nxt + A_BYTES + (wave + ii * NWV) * 1024);
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
@@ -114,10 +114,10 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm_deep_kernel(const GemmArgs
 #pragma unroll
     for (int ii = 0; ii < A_PW; ++ii) {
       const int q = wave + ii * NWV;
-      if (A_PIECES % NWV == 0 || q < A_PIECES) glds16<0>(Ab + a_off[ii] + kb, st + q * 1024);
+      if (A_PIECES % NWV == 0 || q < A_PIECES) glds16(Ab + a_off[ii] + kb, st + q * 1024);
     }
 #pragma unroll
-    for (int ii = 0; ii < W_PW; ++ii) glds16<0>(Wb + w_off[ii] + kb, st + A_BYTES + (wave + ii * NWV) * 1024);
+    for (int ii = 0; ii < W_PW; ++ii) glds16(Wb + w_off[ii] + kb, st + A_BYTES + (wave + ii * NWV) * 1024);
   }
   float2* const rstat = (float2*)(smem + SM::STATS_OFF);
   if constexpr (Epi::ROWSTATS) ln_stage<NT, Epi::STAGE_AFF, (BM + NT / 4 - 1) / (NT / 4)>(epi.ln, epi.ctl.wscale, m0, BM, M, rstat, tid);

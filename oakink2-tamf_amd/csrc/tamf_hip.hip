@@ -20,11 +20,6 @@
 #include "tamf_gemm.h"
 #include "tamf_gemm_clip.h"
 #include "tamf_gemm_deep.h"
-#if defined(TAMF_BENCH) && !defined(TAMF_OVERLAP_PROBE)
-#define TAMF_OVERLAP_PROBE  // (-DTAMF_OVERLAP_PROBE alone: the probe without the ablation code of -DTAMF_BENCH, which spills in some bf16 / f32 instantiations)
-#endif
-#ifdef TAMF_BENCH  // the row-block LayerNorm GEMM of round 4 (measured, not faster: DESIGN.md): an A/B partner of the measurement builds only
-#endif
 #include "tamf_geom.h"
 #include "tamf_misc.h"
 #include "tamf_encoder.h"
@@ -153,12 +148,6 @@ struct tamf_ctx : Workspaces {
   bool graph_in_flight = false;
   int sched_cap = 0;  // allocated length of c1 / c2 / sigma
   int graph_captures = 0, graph_launches_last_loop = 0;  // tamf_loop_stats
-#ifdef TAMF_OVERLAP_PROBE
-  // overlap probe (selection bit 256, measurement builds only): see PingPong
-  std::vector<hipEvent_t> pp_ev;
-  long pp_count = 0;
-  bool pp_on = false;
-#endif
   int step_kernels = 0;
   // per-launch profiling (tamf_step_profile)
   bool prof_on = false;
@@ -286,9 +275,6 @@ static int upload_operand(tamf_ctx* ctx, int prec, const float* w, int N, int K,
       (void)std::frexp(mx, &e);  // mx = m 2^e, m in [0.5, 1)
       wexp = std::min(120, std::max(-120, 15 - e));
     }
-#ifdef TAMF_NO_PRESCALE  // (A/B builds: the unscaled split of rounds 2 - 3; weights beyond 65504 then turn into inf)
-    wexp = 0;
-#endif
     out->inv_scale = std::ldexp(1.0f, -wexp);
     // One power of two per tensor: a weight smaller than 2^-17.5 of the tensor's maximum has an fp16-SUBNORMAL lo part again (fewer than
     // 22 significand bits).  Ordinary tensors are nowhere near (max / typical ~ 2^3 .. 2^7); one huge outlier over ordinary weights is
@@ -348,18 +334,14 @@ static int g_krot = -1;
 // kernel-selection overrides for A/B measurements (tamf_set_gemm_tuning bits 20..): 1 = no clip tiles at all,
 // 2 = FFN2 / out-proj on the 128 x 128 tiles, 4 = attention split once more, 8 = FFN1 on the 128 x 128 tiles,
 // 16 = residual GEMMs of a few clips on the clip / 128 x 128 tiles too (no 32- / 64-row tiles), 64 = f32: QKV on the 128 x 128 tiles,
-// 32 = FFN1 (whole-clip tiles in two or more exact rounds): column-split rounds toggled against TAMF_CLIP_COLSPLIT_DEFAULT,
-// 256 = (-DTAMF_OVERLAP_PROBE / -DTAMF_BENCH builds only) OVERLAP PROBE: the launches of a no-graph loop alternate between two streams with no data
-//       dependency enforced - garbage samples, the time is an upper bound of what removing the kernel boundaries could gain (PingPong),
+// 32 = FFN1 (whole-clip tiles in two or more exact rounds): column-split rounds (off without the bit: they cut FFN1's fetch
+//      by 6.6 % and make the step 0.6 % (f16x3) / 2.3 % (bf16) slower),
 // 512 = streaming attention kernel in the 16-bit modes too,
 // 1024 = clip tiles from 50 % (not 74 %) of the workgroup slots of their rounds.
 // (Rounds 2 - 5 also had 16 (another meaning) / 256 / 2048 / 4096: the LayerNorm-fused 64 x d tile, the GEMM + LayerNorm-kernel form and the row-block kernel
 // of the residual GEMMs - gone with the deferred LayerNorm, which every mode uses now; 32 / 128: clip-tile variants of FFN1 / QKV that
-// lost their A/B.  The bits are accepted and ignored.)
+// lost their A/B; 256 (another meaning): the overlap probe of round 6, measured and removed - DESIGN.md section 6.  The bits are accepted and ignored.)
 static int g_sel = 0;
-#ifndef TAMF_CLIP_COLSPLIT_DEFAULT  // FFN1's rounds split by columns (selection bit 32 toggles it against this default: A/B)
-#define TAMF_CLIP_COLSPLIT_DEFAULT 0
-#endif
 static inline int krot_for(bool ln_tile) { return g_krot >= 0 ? g_krot : (ln_tile ? (4 << 8) : 0); }
 
 // resident workgroup slots of the chip for the 2-per-CU tiles (MI355X: 256 CUs); one "round" of a launch.  Per DEVICE (one
@@ -379,11 +361,11 @@ struct GemmLaunch {
   // wave grid: the 64-row LayerNorm tiles own a CU and run 8 waves (2 x 4), the 64 x 512 one 16 waves (2 x 8: four waves
   // per SIMD cover each other's LDS / barrier latency, 36.6 -> 35.1 us for out-proj); the 128 x 128 tiles run 8 waves
   // (4 x 2) with two workgroups per CU
-#ifndef TAMF_WGM128  // waves along M of the 128 x 128 tiles: 4 = 8 waves per workgroup (4 x 2), two workgroups per CU = 4 waves per SIMD.
-#define TAMF_WGM128 4  // Round 3, two builds alternating on one box: QKV 62.8 -> 60.7 us (f16x3), 31.5 -> 29.6 us (bf16) against the 2 x 2
-#endif                 // grid of rounds 1 - 2; the whole step -1 %: a workgroup left alone on its CU during its partner's epilogue keeps 2 waves per SIMD
+  // waves along M of the 128 x 128 tiles: 4 = 8 waves per workgroup (4 x 2), two workgroups per CU = 4 waves per SIMD.
+  // Round 3, two builds alternating on one box: QKV 62.8 -> 60.7 us (f16x3), 31.5 -> 29.6 us (bf16) against the 2 x 2
+  // grid of rounds 1 - 2; the whole step -1 %: a workgroup left alone on its CU during its partner's epilogue keeps 2 waves per SIMD
   static constexpr int WGN = (BM <= 64) ? (BN == 512 ? 8 : 4) : 2;
-  static constexpr int WGM = (BM <= 64 || Op::PREC == 0) ? 2 : TAMF_WGM128;  // (f32: the 2 x 2 grid stays - input_merge.2 78 us against 91 us with 4 x 2)
+  static constexpr int WGM = (BM <= 64 || Op::PREC == 0) ? 2 : 4;  // (f32: the 2 x 2 grid stays - input_merge.2 78 us against 91 us with 4 x 2)
   template <int SPLIT>
   static hipError_t prepare1() {
     return hipFuncSetAttribute((const void*)gemm_kernel<Op, BM, BN, WGM, WGN, Epi, SPLIT>,
@@ -498,23 +480,17 @@ static bool small_m_launch(const GemmArgs<Op>& ga, const Epi& ep, hipStream_t st
 // row tiles of the X waves (the K tile's loaders): they carry the DMA issue, so they get fewer of the row tiles - 6 of 13 / 5 of 11
 // at 256 columns (5 : 8 spills the Y waves), 2 at 128 columns (a loader wave is blocked ~850 of the ~1 900 cycles of a 128-column
 // interval while its pieces queue; FFN2 at B = 64: 73.7 us with 4 : 9, 69.5 us with 2 : 11)
-#ifndef TAMF_CLIP_XSUB_N2  // (build-time knobs of the A/B runs)
-#define TAMF_CLIP_XSUB_N2 2
-#endif
-#ifndef TAMF_CLIP_XSUB_N4  // X row tiles of a 13-row-tile clip at 256 columns; an 11-row-tile clip gets one less
-#define TAMF_CLIP_XSUB_N4 6
-#endif
-#ifndef TAMF_CLIP_XSUB_PARTS  // X : Y row tiles of the 7- / 6-row-tile parts (A/B knob; FFN2 at B = 32: 2 : 5 46 us, 3 : 4 60 us, 4 : 3 slower still)
-#define TAMF_CLIP_XSUB_PARTS 2
-#endif
-#ifndef TAMF_CLIP_YSUB_F32_N4  // f32 at 256 columns: row tiles of the Y waves (6: they read the next K tile's fragments inside their MFMA stream,
-#define TAMF_CLIP_YSUB_F32_N4 6  // clip_mma_read_y, which does not fit the registers with 7; in f32 nothing of X overlaps Y's MFMAs, so the split is free)
-#endif
 template <int NI, int NSUB, int PARTS, int PREC>
 struct ClipXsub {
-  static constexpr int value = PARTS > 1 ? TAMF_CLIP_XSUB_PARTS
-                               : NI >= 4 ? (PREC == 0 ? NSUB - TAMF_CLIP_YSUB_F32_N4 : TAMF_CLIP_XSUB_N4 - (13 - NSUB + 1) / 2)
-                                         : TAMF_CLIP_XSUB_N2;
+  static constexpr int XSUB_N2 = 2;
+  static constexpr int XSUB_N4 = 6;  // X row tiles of a 13-row-tile clip at 256 columns; an 11-row-tile clip gets one less
+  static constexpr int XSUB_PARTS = 2;  // X : Y row tiles of the 7- / 6-row-tile parts (FFN2 at B = 32: 2 : 5 46 us, 3 : 4 60 us, 4 : 3 slower still)
+  // f32 at 256 columns: row tiles of the Y waves (6: they read the next K tile's fragments inside their MFMA stream,
+  // clip_mma_read_y, which does not fit the registers with 7; in f32 nothing of X overlaps Y's MFMAs, so the split is free)
+  static constexpr int YSUB_F32_N4 = 6;
+  static constexpr int value = PARTS > 1 ? XSUB_PARTS
+                               : NI >= 4 ? (PREC == 0 ? NSUB - YSUB_F32_N4 : XSUB_N4 - (13 - NSUB + 1) / 2)
+                                         : XSUB_N2;
 };
 // NSUB: row tiles of a TILE.  PARTS = 1: the tile is a whole clip; PARTS = 2: every clip is cut into its first NSUB row tiles and
 // the rest (NSUB or NSUB - 1 of them), each a tile of its own - for launches whose whole-clip tiles would fill at most half of the CUs
@@ -559,7 +535,7 @@ struct ClipLaunch {
     {  // column-split rounds (tamf_gemm_clip.h, ClipGemmArgs::colsplit): whole clips, two or more EXACT rounds, column tiles divisible
       const int ntn = N / C::BN, rounds = ga.n_tiles / cus;
       const bool fits = PARTS == 1 && ga.n_tiles > cus && ga.n_tiles % cus == 0 && ntn % rounds == 0 && NI == 4;
-      if (fits && (TAMF_CLIP_COLSPLIT_DEFAULT != 0) != ((g_sel & 32) != 0)) ga.colsplit = ntn;
+      if (fits && (g_sel & 32)) ga.colsplit = ntn;
     }
     hipLaunchKernelGGL((clip_gemm_kernel<Op, NSUB, NI, XSUB, Epi>), dim3(ga.n_tiles < cus ? ga.n_tiles : cus), dim3(512), C::BYTES, st, ga, epi);
     return hipGetLastError();
@@ -661,9 +637,6 @@ static hipError_t prepare_all() {
   return hipSuccess;
 }
 
-#ifndef TAMF_ATTN_KSPLIT  // (0: A/B builds without the key split of the last query tile)
-#define TAMF_ATTN_KSPLIT 1
-#endif
 template <class Op>
 static hipError_t launch_attn(const AttnArgs<Op>& aa, int B, int hd, hipStream_t st) {
   const int nqt = (aa.Sp + 15) / 16;
@@ -691,7 +664,7 @@ static hipError_t launch_attn(const AttnArgs<Op>& aa, int B, int hd, hipStream_t
     /* (whether the split applies is decided on the WORST case of the query split - one workgroup, nqt - 1 tile-owning waves: the  */ \
     /*  partial area grows with them and the four extra waves then sit at nqt + 3 - so it cannot apply at one batch size and not  */ \
     /*  at another)                                                                                                     */ \
-    if (TAMF_ATTN_KSPLIT && Op::PREC == 0 && nqt % 4 == 1 && nqt >= 5 && nqt + 3 <= AttnRes<Op, HD_, NKB_>::MAXW &&            \
+    if (Op::PREC == 0 && nqt % 4 == 1 && nqt >= 5 && nqt + 3 <= AttnRes<Op, HD_, NKB_>::MAXW &&            \
         AttnRes<Op, HD_, NKB_>::ksplit_extra(aa.S, aa.Sp, nqt - 1) >= 0) {                                 \
       const int nwq = (nqt - 1 + chunks - 1) / chunks, nlast = nqt - 1 - (chunks - 1) * nwq > 0 ? nqt - 1 - (chunks - 1) * nwq : 0; \
       /* the four key-split waves go to the SIMDs with the fewest tiles in the last workgroup (wave w runs on SIMD w mod 4) */     \
@@ -948,9 +921,6 @@ extern "C" void tamf_ctx_destroy(tamf_ctx* ctx) {
   if (ctx->graph_exec) (void)hipGraphExecDestroy(ctx->graph_exec);
   if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
   if (ctx->cap_stream) (void)hipStreamDestroy(ctx->cap_stream);
-#ifdef TAMF_OVERLAP_PROBE
-  for (hipEvent_t e : ctx->pp_ev) (void)hipEventDestroy(e);
-#endif
   for (void* p : ctx->allocs) (void)hipFree(p);
   for (void* p : ctx->ws_allocs) (void)hipFree(p);
   delete ctx;
@@ -1466,32 +1436,6 @@ extern "C" int tamf_set_cond_ragged(tamf_ctx* ctx, int32_t B, int32_t T, int32_t
 // ------------------------------------------------------------------------------------------------
 // one denoiser evaluation = the kernel sequence below (captured into a hipGraph by the sampling loop)
 // ------------------------------------------------------------------------------------------------
-#ifdef TAMF_OVERLAP_PROBE
-// OVERLAP PROBE (-DTAMF_OVERLAP_PROBE measurement builds only; tamf_set_gemm_tuning selection bit 256; plain launches, no hipGraph).  What would a step gain
-// if launch k + 1 could start on the CUs that launch k has left, instead of behind the kernel boundary - the most that per-clip ready
-// flags / a persistent per-clip pipeline could recover?  The launches of the loop alternate between the caller's stream and the
-// context's second stream, and NOTHING enforces their data dependencies: the SAMPLES ARE GARBAGE, only the time means something, and
-// it is an upper bound (a real consumer waits for its producers' tiles; here it waits for nothing).  Order of dispatch is kept sane:
-// launch k becomes eligible when launch k - 2 (same stream) and launch k - 3 are complete - i.e. never before launch k - 1 became
-// eligible - so at most two launches share the chip, the older one placed first (gfx950 / ROCm 7.2 ignores hipExtAnyOrderLaunch on
-// one stream: tools/micro/anyorder.hip, profiles/r06/anyorder_c01.txt).
-struct PingPong {
-  tamf_ctx* c;
-  hipStream_t a, b;
-  hipStream_t next() {
-    if (!c->pp_on) return a;
-    const long k = c->pp_count++;
-    hipStream_t s = (k & 1) ? b : a;
-    const size_t NEV = c->pp_ev.size() - 1;  // (the last event is the loop's fork / join)
-    (void)hipEventRecord(c->pp_ev[k % NEV], s);  // fires when everything launched on s before launch k is complete
-    if (k > 0) (void)hipStreamWaitEvent(s, c->pp_ev[(k - 1) % NEV], 0);  // ... and launch k waits for what launch k - 1 waited for
-    return s;
-  }
-};
-#define TAMF_NEXT_STREAM pp_.next()
-#else
-#define TAMF_NEXT_STREAM st
-#endif
 // residual GEMM of the deferred-LayerNorm form (out-proj, FFN2; 16-bit modes): the clip's row parts where whole clips would fill at
 // most half of the CUs, whole-clip tiles where they fill at least half of their rounds' slots, 128 x 128 tiles for every other shape -
 // the same K order per element and the same statistics trees in all three, i.e. the same bits
@@ -1533,9 +1477,6 @@ static int enqueue_step(tamf_ctx* ctx, hipStream_t st, const EpiHead<Op>& head_i
   typedef typename Op::elem_t E;
   const int d = ctx->d, ff = ctx->ff, B = ctx->B, T = ctx->T, S = ctx->S, Sp = ctx->Sp, M = ctx->M, P = ctx->P;
   int nk = 0;
-#ifdef TAMF_OVERLAP_PROBE
-  PingPong pp_{ctx, st, ctx->cap_stream};
-#endif
   // algorithmic FLOPs of the reference work each launch stands for (true S, not padded rows)
   const double BS = (double)B * S, BT = (double)B * T, dd = d, F = ctx->F;
   auto mark = [&](const char* name, double flops) {
@@ -1549,22 +1490,20 @@ static int enqueue_step(tamf_ctx* ctx, hipStream_t st, const EpiHead<Op>& head_i
     ctx->prof_flops.push_back(flops);
   };
   {  // input_merge.0 on [pose | (h2o)] with the hoisted object term, SiLU
-    hipStream_t sk = TAMF_NEXT_STREAM;
     GemmArgs<Op> ga{(const E*)ctx->xs_op.p, ctx->XK, (const E*)ctx->Wfused.p, ctx->XK, B * T, d, ctx->XK, 0};
     EpiBiasAct<Op> ep{nullptr, ctx->cobj, d, (E*)ctx->h1_op.p, d, ACT_SILU, {ctx->Wfused.inv_scale, ctx->status}};
-    HIPCHK(ctx, gemm128<Op>(ga, ep, sk));
+    HIPCHK(ctx, gemm128<Op>(ga, ep, st));
     mark("gemm_input_merge0", BT * (2.0 * F * dd + 2.0 * dd * (ctx->arch.kind == TAMF_KIND_R ? 3 : 2) * dd +
                                     (ctx->arch.kind == TAMF_KIND_R ? 2.0 * ctx->arch.h2o_dim * dd : 0.0)));
   }
   {  // input_merge.2 + nan_to_num + positional rows -> token rows of X
-    hipStream_t sk = TAMF_NEXT_STREAM;
     GemmArgs<Op> ga{(const E*)ctx->h1_op.p, d, (const E*)ctx->Wm2.p, d, B * T, d, d, 0};
     // (+ the prefix and pad rows of every clip, written by the tile that holds the clip's first frame)
     const float* temb_now = (ctx->in_loop && ctx->tmap_on) ? ctx->temb_loop : ctx->temb;
     EpiSeqRows<Op> ep{ctx->bm2, ctx->pe + (long)P * d, d, ctx->X, (E*)ctx->X_st, d, T, Sp, P, ctx->pstatic, temb_now, ctx->tcur, ctx->has_t, S, t_off, {ctx->Wm2.inv_scale, ctx->status}};
     hipError_t es = hipSuccess;
-    if (small_m_launch<Op>(ga, ep, sk, &es)) HIPCHK(ctx, es);
-    else HIPCHK(ctx, gemm128<Op>(ga, ep, sk));
+    if (small_m_launch<Op>(ga, ep, st, &es)) HIPCHK(ctx, es);
+    else HIPCHK(ctx, gemm128<Op>(ga, ep, st));
     mark("gemm_input_merge2", BT * 2.0 * dd * dd + (ctx->has_t ? B * 4.0 * dd * dd : 0.0));
   }
   const float qscale = 1.4426950408889634f / sqrtf((float)ctx->hd);
@@ -1579,7 +1518,6 @@ static int enqueue_step(tamf_ctx* ctx, hipStream_t st, const EpiHead<Op>& head_i
         const LnStats ln_in{l ? ctx->stat_ffn : nullptr, NB, inv_d, 1e-5f};  // the LayerNorm in front of the attention block (layer 0: none)
         const LnStats ln_ff{ctx->stat_att, NB, inv_d, 1e-5f};               // ... in front of the feed-forward block
         {
-          hipStream_t sk = TAMF_NEXT_STREAM;
           GemmArgs<Op> ga{(const E*)ctx->X_op.p, d, (const E*)w.Win.p, d, M, 3 * d, d, 0};
           bool on_clip = false;
           if constexpr (Op::PREC == 0) {  // f32: the Q | K columns and the V columns as two clip launches (see the other branch)
@@ -1588,14 +1526,13 @@ static int enqueue_step(tamf_ctx* ctx, hipStream_t st, const EpiHead<Op>& head_i
                 if (ClipLaunch<Op, 2, EpiQK<Op, true>, NS>::applies(B, Sp, 2 * d, d) && ClipLaunch<Op, 2, EpiVt<Op, true>, NS>::applies(B, Sp, d, d)) {
                   EpiQK<Op, true> eq{w.c2_in, (E*)ctx->QK_op.p, d, qscale, ACT_NONE, {w.Win.inv_scale, ctx->status}, ln_in};
                   if (ClipLaunch<Op, 4, EpiQK<Op, true>, NS>::applies(B, Sp, 2 * d, d))
-                    HIPCHK(ctx, (ClipLaunch<Op, 4, EpiQK<Op, true>, NS>::launch(nullptr, ga.A, d, ga.W, d, B, Sp, 2 * d, d, eq, sk)));
+                    HIPCHK(ctx, (ClipLaunch<Op, 4, EpiQK<Op, true>, NS>::launch(nullptr, ga.A, d, ga.W, d, B, Sp, 2 * d, d, eq, st)));
                   else
-                    HIPCHK(ctx, (ClipLaunch<Op, 2, EpiQK<Op, true>, NS>::launch(nullptr, ga.A, d, ga.W, d, B, Sp, 2 * d, d, eq, sk)));
+                    HIPCHK(ctx, (ClipLaunch<Op, 2, EpiQK<Op, true>, NS>::launch(nullptr, ga.A, d, ga.W, d, B, Sp, 2 * d, d, eq, st)));
                   const E* Wv = (const E*)((const char*)w.Win.p + (size_t)2 * d * d * Op::EB);
                   EpiVt<Op, true> ev{w.c2_in + 2 * d, (E*)ctx->Vt_op.p, ctx->H, ctx->hd, ctx->Skp, ACT_NONE, {w.Win.inv_scale, ctx->status}, ln_in};
                   mark("gemm_qk", BS * 2.0 * dd * 2 * dd);
-                  sk = TAMF_NEXT_STREAM;
-                  HIPCHK(ctx, (ClipLaunch<Op, 2, EpiVt<Op, true>, NS>::launch(nullptr, ga.A, d, Wv, d, B, Sp, d, d, ev, sk)));
+                  HIPCHK(ctx, (ClipLaunch<Op, 2, EpiVt<Op, true>, NS>::launch(nullptr, ga.A, d, Wv, d, B, Sp, d, d, ev, st)));
                   mark("gemm_v", BS * 2.0 * dd * dd);
                   on_clip = true;
                 }
@@ -1605,49 +1542,45 @@ static int enqueue_step(tamf_ctx* ctx, hipStream_t st, const EpiHead<Op>& head_i
           if (!on_clip) {
             EpiQKV<Op, true> ep{w.c2_in, (E*)ctx->QK_op.p, (E*)ctx->Vt_op.p, d, ctx->H, ctx->hd, Sp, ctx->Skp, qscale, {w.Win.inv_scale, ctx->status}, ln_in};
             hipError_t es = hipSuccess;
-            if (small_m_launch<Op>(ga, ep, sk, &es)) HIPCHK(ctx, es);
-            else HIPCHK(ctx, gemm128<Op>(ga, ep, sk));
+            if (small_m_launch<Op>(ga, ep, st, &es)) HIPCHK(ctx, es);
+            else HIPCHK(ctx, gemm128<Op>(ga, ep, st));
             mark("gemm_qkv", BS * 2.0 * dd * 3 * dd);
           }
         }
         {
-          hipStream_t sk = TAMF_NEXT_STREAM;
           AttnArgs<Op> aa{(const E*)ctx->QK_op.p, (const E*)ctx->Vt_op.p, (E*)ctx->A_op.p, S, Sp, ctx->Skp, d, ctx->H, 0};
-          HIPCHK(ctx, launch_attn<Op>(aa, B, ctx->hd, sk));
+          HIPCHK(ctx, launch_attn<Op>(aa, B, ctx->hd, st));
           mark("attention", 4.0 * B * (double)S * S * dd);
         }
         {
-          hipStream_t sk = TAMF_NEXT_STREAM;
           GemmArgs<Op> ga{(const E*)ctx->A_op.p, d, (const E*)w.Wout.p, d, M, d, d, 0};
           EpiResid<Op> ep{w.bb_att, w.g_att, ctx->X, (E*)ctx->X_st, d, ctx->stat_att, ACT_NONE, {w.Wout.inv_scale, ctx->status}, ln_in};
-          HIPCHK(ctx, launch_resid<Op>(ga, ep, B, Sp, sk));
+          HIPCHK(ctx, launch_resid<Op>(ga, ep, B, Sp, st));
           mark("gemm_outproj", BS * 2.0 * dd * dd);
         }
         {
-          hipStream_t sk = TAMF_NEXT_STREAM;
           GemmArgs<Op> ga{(const E*)ctx->X_op.p, d, (const E*)w.W1.p, d, M, ff, d, 0};
           EpiBiasAct<Op, true> ep{w.c2_ff, nullptr, 0, (E*)ctx->H_op.p, ff, ACT_GELU, {w.W1.inv_scale, ctx->status}, ln_ff};
           bool on_clip = false;
           if (!(g_sel & 8)) {
             TAMF_CLIP_NSUB(Sp, {
               if (ClipLaunch<Op, 4, EpiBiasAct<Op, true>, NS>::applies(B, Sp, ff, d)) {
-                HIPCHK(ctx, (ClipLaunch<Op, 4, EpiBiasAct<Op, true>, NS>::launch(nullptr, ga.A, d, ga.W, d, B, Sp, ff, d, ep, sk)));
+                HIPCHK(ctx, (ClipLaunch<Op, 4, EpiBiasAct<Op, true>, NS>::launch(nullptr, ga.A, d, ga.W, d, B, Sp, ff, d, ep, st)));
                 on_clip = true;
               }
             })
           }
           if (!on_clip) {
             hipError_t es = hipSuccess;
-            if (small_m_launch<Op>(ga, ep, sk, &es)) HIPCHK(ctx, es);
-            else HIPCHK(ctx, gemm128<Op>(ga, ep, sk));
+            if (small_m_launch<Op>(ga, ep, st, &es)) HIPCHK(ctx, es);
+            else HIPCHK(ctx, gemm128<Op>(ga, ep, st));
           }
           mark("gemm_ffn1_gelu", BS * 2.0 * dd * ff);
         }
         {
-          hipStream_t sk = TAMF_NEXT_STREAM;
           GemmArgs<Op> ga{(const E*)ctx->H_op.p, ff, (const E*)w.W2.p, ff, M, d, ff, 0};
           EpiResid<Op> ep{w.bb_ffn, w.g_ffn, ctx->X, (E*)ctx->X_st, d, ctx->stat_ffn, ACT_NONE, {w.W2.inv_scale, ctx->status}, ln_ff};
-          HIPCHK(ctx, launch_resid<Op>(ga, ep, B, Sp, sk));
+          HIPCHK(ctx, launch_resid<Op>(ga, ep, B, Sp, st));
           mark("gemm_ffn2", BS * 2.0 * dd * ff);
         }
       }
@@ -1655,13 +1588,12 @@ static int enqueue_step(tamf_ctx* ctx, hipStream_t st, const EpiHead<Op>& head_i
   }
   {
     // N = 128 is a single column tile: 64-row tiles (8 waves) double the workgroups that share the Philox-heavy epilogue
-    hipStream_t sk = TAMF_NEXT_STREAM;
     GemmArgs<Op> ga{(const E*)ctx->X_op.p, d, (const E*)ctx->Wf.p, d, M, ctx->XN, d, 0};
     EpiHead<Op> head = head_in;
     head.t_off = t_off;
     hipError_t es = hipSuccess;
-    if (small_m_launch<Op>(ga, head, sk, &es)) HIPCHK(ctx, es);  // (a few clips per call)
-    else HIPCHK(ctx, (GemmLaunch<Op, 64, 128, EpiHead<Op>>::launch(ga, head, sk)));
+    if (small_m_launch<Op>(ga, head, st, &es)) HIPCHK(ctx, es);  // (a few clips per call)
+    else HIPCHK(ctx, (GemmLaunch<Op, 64, 128, EpiHead<Op>>::launch(ga, head, st)));
     mark("gemm_head_ddpm", BT * 2.0 * dd * F);
   }
   ctx->step_kernels = nk;
@@ -1775,32 +1707,10 @@ static int loop_impl(tamf_ctx* ctx, const float* noise, uint64_t seed, int64_t c
   hipLaunchKernelGGL(set_loop_params_kernel, dim3(1), dim3(64), 0, st, ctx->loop_params, noise, dump, (long)B * ctx->F * T,
                      (unsigned long long)seed, (long long)clip_base);
   if (!use_graph) {
-#ifdef TAMF_OVERLAP_PROBE
-    ctx->pp_on = (g_sel & 256) != 0;
-    if (ctx->pp_on) {  // the second stream starts behind the loop's set-up kernels
-      if (ctx->pp_ev.empty()) {
-        ctx->pp_ev.resize(64);
-        for (auto& e : ctx->pp_ev) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      }
-      ctx->pp_count = 0;
-      HIPCHK(ctx, hipEventRecord(ctx->pp_ev[63], st));
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->cap_stream, ctx->pp_ev[63], 0));
-    }
-#endif
     for (int i = 0; i < N; ++i) {
       TRY(enqueue_step<Op>(ctx, st, h));
-#ifdef TAMF_OVERLAP_PROBE
-      if (ctx->pp_on) { PingPong pp_{ctx, st, ctx->cap_stream}; hipLaunchKernelGGL(advance_t_kernel, grid1d(B), dim3(256), 0, pp_.next(), ctx->tcur, B, 1); continue; }
-#endif
       hipLaunchKernelGGL(advance_t_kernel, grid1d(B), dim3(256), 0, st, ctx->tcur, B, 1);
     }
-#ifdef TAMF_OVERLAP_PROBE
-    if (ctx->pp_on) {  // join: the caller's stream continues behind both
-      HIPCHK(ctx, hipEventRecord(ctx->pp_ev[63], ctx->cap_stream));
-      HIPCHK(ctx, hipStreamWaitEvent(st, ctx->pp_ev[63], 0));
-      ctx->pp_on = false;
-    }
-#endif
   } else {
     // G consecutive steps per graph (the largest divisor of N up to 16: 10 for N = 1000 -> 100 graph launches per loop);
     // the sequence is step-agnostic (device-side step counter) and seed-agnostic (LoopParams), so it is captured once per

@@ -221,6 +221,10 @@ class TamfContext:
         except Exception:
             pass
 
+    def _check(self, rc: int):
+        """raise for a non-zero return code, with the error string of this context in the library it was created in"""
+        _check(rc, self._h, self._L)
+
     # -- weights ------------------------------------------------------------------------------
     def load_state_dict(self, sd: Mapping[str, torch.Tensor], max_timesteps: int = 5000, strict_weight_range: bool = False):
         """max_timesteps = rows of the timestep-embedding table; the default covers every t the reference's
@@ -234,9 +238,9 @@ class TamfContext:
                 continue
             h = t.detach().to("cpu", torch.float32).contiguous()
             shape = (c_int64 * max(h.dim(), 1))(*(list(h.shape) or [1]))
-            _check(L.tamf_load_weight(self._h, name.encode(), c_void_p(h.data_ptr()), shape, max(h.dim(), 1)), self._h, self._L)
+            self._check(L.tamf_load_weight(self._h, name.encode(), c_void_p(h.data_ptr()), shape, max(h.dim(), 1)))
         with torch.cuda.device(self.device):
-            _check(L.tamf_finalize_weights(self._h, int(max_timesteps), c_void_p(_stream_ptr(self.device))), self._h, self._L)
+            self._check(L.tamf_finalize_weights(self._h, int(max_timesteps), c_void_p(_stream_ptr(self.device))))
         if strict_weight_range and self.precision == "f16x3" and (self.status_flags(clear=False) & STATUS_F16_WEIGHT_RANGE):
             note = L.tamf_last_error(self._h)
             raise TamfRangeError(note.decode() if note else "f16x3: a weight tensor's dynamic range exceeds the split-fp16 format")
@@ -249,14 +253,14 @@ class TamfContext:
         lv = np.ascontiguousarray(log_variance_clipped, dtype=np.float64)
         assert c1.shape == c2.shape == lv.shape and c1.ndim == 1
         self.n_steps = int(c1.shape[0])
-        _check(self._L.tamf_set_schedule(self._h, self.n_steps, c1.ctypes.data_as(c_void_p), c2.ctypes.data_as(c_void_p),
-                                       lv.ctypes.data_as(c_void_p)), self._h)
+        self._check(self._L.tamf_set_schedule(self._h, self.n_steps, c1.ctypes.data_as(c_void_p), c2.ctypes.data_as(c_void_p),
+                                            lv.ctypes.data_as(c_void_p)))
         if timestep_map is not None:
             tm = np.ascontiguousarray(timestep_map, dtype=np.int32)
             assert tm.shape == (self.n_steps,), (tm.shape, self.n_steps)
             if not np.array_equal(tm, np.arange(self.n_steps, dtype=np.int32)):
                 with torch.cuda.device(self.device):
-                    _check(self._L.tamf_set_timestep_map(self._h, self.n_steps, tm.ctypes.data_as(c_void_p)), self._h, self._L)
+                    self._check(self._L.tamf_set_timestep_map(self._h, self.n_steps, tm.ctypes.data_as(c_void_p)))
 
     # -- conditioning -------------------------------------------------------------------------
     def set_cond(self, text_embedding: Optional[torch.Tensor], hand_side: Sequence, shape: torch.Tensor,
@@ -279,16 +283,16 @@ class TamfContext:
                 raise ValueError(f"obj_num must hold one count per clip: shape {num_np.shape} for B = {B}")
         if num_np is None and not hasattr(self._L, "tamf_set_cond_ragged"):  # (an older A/B build loaded through _lib.load_from)
             with torch.cuda.device(dev):
-                _check(self._L.tamf_set_cond(self._h, B, T, nobj, c_void_p(te.data_ptr() if te is not None else 0), side_np.ctypes.data_as(c_void_p),
-                                           c_void_p(sh.data_ptr()), c_void_p(oe.data_ptr()), c_void_p(ot.data_ptr()), c_void_p(_stream_ptr(dev))), self._h)
+                self._check(self._L.tamf_set_cond(self._h, B, T, nobj, c_void_p(te.data_ptr() if te is not None else 0), side_np.ctypes.data_as(c_void_p),
+                                                c_void_p(sh.data_ptr()), c_void_p(oe.data_ptr()), c_void_p(ot.data_ptr()), c_void_p(_stream_ptr(dev))))
             self._keep = [te, sh, oe, ot]
             self.B, self.T = int(B), int(T)
             return
         with torch.cuda.device(dev):
-            _check(self._L.tamf_set_cond_ragged(self._h, B, T, nobj, num_np.ctypes.data_as(c_void_p) if num_np is not None else c_void_p(0),
-                                              c_void_p(te.data_ptr() if te is not None else 0), side_np.ctypes.data_as(c_void_p),
-                                              c_void_p(sh.data_ptr()), c_void_p(oe.data_ptr()), c_void_p(ot.data_ptr()),
-                                              c_void_p(_stream_ptr(dev))), self._h)
+            self._check(self._L.tamf_set_cond_ragged(self._h, B, T, nobj, num_np.ctypes.data_as(c_void_p) if num_np is not None else c_void_p(0),
+                                                   c_void_p(te.data_ptr() if te is not None else 0), side_np.ctypes.data_as(c_void_p),
+                                                   c_void_p(sh.data_ptr()), c_void_p(oe.data_ptr()), c_void_p(ot.data_ptr()),
+                                                   c_void_p(_stream_ptr(dev))))
         self._keep = [te, sh, oe, ot]
         self.B, self.T = int(B), int(T)
 
@@ -311,8 +315,8 @@ class TamfContext:
             raise IndexError(f"timestep {lo if lo < 0 else hi} outside the timestep-embedding table [0, {self.max_timesteps})")
         out = torch.empty_like(xd)
         with torch.cuda.device(dev):
-            _check(self._L.tamf_denoise(self._h, c_void_p(xd.data_ptr()), c_void_p(td.data_ptr()), c_void_p(out.data_ptr()),
-                                      c_void_p(_stream_ptr(dev))), self._h)
+            self._check(self._L.tamf_denoise(self._h, c_void_p(xd.data_ptr()), c_void_p(td.data_ptr()), c_void_p(out.data_ptr()),
+                                           c_void_p(_stream_ptr(dev))))
         self._raise_on_range()
         return out
 
@@ -341,10 +345,10 @@ class TamfContext:
         enc = torch.empty(B, self.latent_dim, dtype=torch.float32, device=dev)
         act = torch.empty(B, F, dtype=torch.float32, device=dev) if with_activation else None
         with torch.cuda.device(dev):
-            _check(self._L.tamf_encode(self._h, B, T, nobj, num_np.ctypes.data_as(c_void_p) if num_np is not None else c_void_p(0),
-                                       c_void_p(pr.data_ptr()), c_void_p(sh.data_ptr()), c_void_p(side_d.data_ptr()), c_void_p(oe.data_ptr()),
-                                       c_void_p(ot.data_ptr()), c_void_p(enc.data_ptr()), c_void_p(act.data_ptr() if act is not None else 0),
-                                       c_void_p(_stream_ptr(dev))), self._h, self._L)
+            self._check(self._L.tamf_encode(self._h, B, T, nobj, num_np.ctypes.data_as(c_void_p) if num_np is not None else c_void_p(0),
+                                            c_void_p(pr.data_ptr()), c_void_p(sh.data_ptr()), c_void_p(side_d.data_ptr()), c_void_p(oe.data_ptr()),
+                                            c_void_p(ot.data_ptr()), c_void_p(enc.data_ptr()), c_void_p(act.data_ptr() if act is not None else 0),
+                                            c_void_p(_stream_ptr(dev))))
         self._keep = [pr, sh, oe, ot, side_d]
         return enc, act
 
@@ -354,9 +358,9 @@ class TamfContext:
         nz = _dev_f32(noise, dev) if noise is not None else None
         out = torch.empty_like(xt)
         with torch.cuda.device(dev):
-            _check(self._L.tamf_ddpm_step(self._h, c_void_p(xt.data_ptr()), c_void_p(x0d.data_ptr()), int(t),
-                                        c_void_p(nz.data_ptr() if nz is not None else 0), c_void_p(out.data_ptr()),
-                                        xt.numel(), c_void_p(_stream_ptr(dev))), self._h)
+            self._check(self._L.tamf_ddpm_step(self._h, c_void_p(xt.data_ptr()), c_void_p(x0d.data_ptr()), int(t),
+                                             c_void_p(nz.data_ptr() if nz is not None else 0), c_void_p(out.data_ptr()),
+                                             xt.numel(), c_void_p(_stream_ptr(dev))))
         return out
 
     def sample_loop(self, noise: Optional[torch.Tensor] = None, seed: int = 0, clip_id_base: int = 0,
@@ -373,10 +377,10 @@ class TamfContext:
             out = torch.empty(shape, device=dev, dtype=torch.float32)
         dmp = torch.empty((self.n_steps,) + shape, device=dev, dtype=torch.float32) if dump else None
         with torch.cuda.device(dev):
-            _check(self._L.tamf_sample_loop(self._h, c_void_p(nz.data_ptr() if nz is not None else 0), int(seed) & (2**64 - 1),
-                                          int(clip_id_base), c_void_p(out.data_ptr()),
-                                          c_void_p(dmp.data_ptr() if dmp is not None else 0), 1 if use_graph else 0,
-                                          c_void_p(_stream_ptr(dev))), self._h)
+            self._check(self._L.tamf_sample_loop(self._h, c_void_p(nz.data_ptr() if nz is not None else 0), int(seed) & (2**64 - 1),
+                                               int(clip_id_base), c_void_p(out.data_ptr()),
+                                               c_void_p(dmp.data_ptr() if dmp is not None else 0), 1 if use_graph else 0,
+                                               c_void_p(_stream_ptr(dev))))
         self._keep_loop = [nz, dmp]
         self._raise_on_range()
         return (out, dmp) if dump else out
@@ -392,15 +396,14 @@ class TamfContext:
         current stream."""
         v = ctypes.c_uint32(0)
         with torch.cuda.device(self.device):
-            _check(self._L.tamf_get_status_flags(self._h, ctypes.byref(v), 1 if clear else 0, c_void_p(_stream_ptr(self.device))),
-                   self._h)
+            self._check(self._L.tamf_get_status_flags(self._h, ctypes.byref(v), 1 if clear else 0, c_void_p(_stream_ptr(self.device))))
         return int(v.value)
 
     def resize(self, max_batch: int, max_frames: int) -> None:
         """Re-dimension the workspaces for (max_batch, max_frames); the uploaded weights and the schedule stay.  Conditioning must be
         set again."""
         with torch.cuda.device(self.device):
-            _check(self._L.tamf_ctx_resize(self._h, int(max_batch), int(max_frames)), self._h, self._L)
+            self._check(self._L.tamf_ctx_resize(self._h, int(max_batch), int(max_frames)))
         self.max_batch, self.max_frames = int(max_batch), int(max_frames)
         self.B = self.T = 0
         self._keep = []
@@ -409,7 +412,7 @@ class TamfContext:
         """Test hook: verify the guard bands around every device allocation of this context (set_guard_bytes() before it was
         created).  Raises TamfError naming the allocations a kernel wrote outside of; returns the number of guarded allocations."""
         n = c_int32(0)
-        _check(self._L.tamf_test_check_guards(self._h, ctypes.byref(n)), self._h, self._L)
+        self._check(self._L.tamf_test_check_guards(self._h, ctypes.byref(n)))
         return int(n.value)
 
     def refine(self, sample_pose_repr: torch.Tensor, h2o_dist: torch.Tensor) -> torch.Tensor:
@@ -419,15 +422,15 @@ class TamfContext:
         assert tuple(h2o.shape) == (self.B, self.T, self.h2o_dim)
         out = torch.empty_like(xin)
         with torch.cuda.device(dev):
-            _check(self._L.tamf_refine(self._h, c_void_p(xin.data_ptr()), c_void_p(h2o.data_ptr()), c_void_p(out.data_ptr()),
-                                     c_void_p(_stream_ptr(dev))), self._h)
+            self._check(self._L.tamf_refine(self._h, c_void_p(xin.data_ptr()), c_void_p(h2o.data_ptr()), c_void_p(out.data_ptr()),
+                                          c_void_p(_stream_ptr(dev))))
         self._raise_on_range()
         return out
 
     def loop_stats(self):
         """(graph captures so far, graph launches of the last sample_loop call)"""
         a, b = c_int32(), c_int32()
-        _check(self._L.tamf_loop_stats(self._h, ctypes.byref(a), ctypes.byref(b)), self._h, self._L)
+        self._check(self._L.tamf_loop_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
         return int(a.value), int(b.value)
 
     @property
@@ -443,7 +446,7 @@ class TamfContext:
         with torch.cuda.device(self.device):
             n = self._L.tamf_step_profile(self._h, max_n, ms, fl, names, c_void_p(_stream_ptr(self.device)))
         if n < 0:
-            _check(n, self._h, self._L)
+            self._check(n)
         out = []
         for i in range(n):
             nm = names.raw[i * 48:(i + 1) * 48].split(b"\0", 1)[0].decode()
@@ -462,7 +465,7 @@ class TamfContext:
             n = self._L.tamf_refine_profile(self._h, c_void_p(xin.data_ptr()), c_void_p(h2o.data_ptr()), c_void_p(out.data_ptr()), max_n,
                                           ms, fl, names, c_void_p(_stream_ptr(dev)))
         if n < 0:
-            _check(n, self._h, self._L)
+            self._check(n)
         return [(names.raw[i * 48:(i + 1) * 48].split(b"\0", 1)[0].decode(), float(ms[i]), float(fl[i])) for i in range(n)]
 
 

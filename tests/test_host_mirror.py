@@ -111,7 +111,20 @@ def test_hooks_are_compiled_through_one_guard():
         assert re.search(r'^extern "C" int %s\(' % sym, hooks, flags=re.M) and not re.search(r'^extern "C" int %s\(' % sym, "\n".join(lines), flags=re.M)
 
 
-@pytest.mark.parametrize("edited,owner", [("csrc/tamf_hip_hooks.h", 0), ("csrc/tamf_voxel.h", 1), ("csrc/tamf_mano.h", 2), ("include/tamf_mano.h", 2)])
+def test_the_sampler_has_five_build_switches():
+    """the TAMF_ identifiers that a preprocessor conditional of the sampler's sources tests (#if / #ifdef / #ifndef / #elif, defined(...)
+    included) are the hooks build, the fallback of the counted waits and the three instruments of tools/ - a decided A/B knob is plain code"""
+    from oakink2_tamf_amd import _lib
+
+    seen = set()
+    for name in _lib.SAMPLER.sources:
+        text = open(os.path.join(_lib.CSRC, name)).read().replace("\\\n", " ")
+        for cond in re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$", text, flags=re.M):
+            seen |= set(re.findall(r"\bTAMF_\w+", cond.split("//")[0]))
+    assert seen == {"TAMF_TEST_HOOKS", "TAMF_BENCH", "TAMF_TIMELINE", "TAMF_TIMELINE_NI", "TAMF_CLIP_SAFE_WAIT"}
+
+
+@pytest.mark.parametrize("edited,owner", [("csrc/tamf_hip_hooks.h", 0),("csrc/tamf_voxel.h", 1), ("csrc/tamf_mano.h", 2), ("include/tamf_mano.h", 2)])
 def test_an_edit_makes_only_its_own_library_stale(edited, owner, tmp_path, monkeypatch):
     """on a copy of csrc/ and include/ with stand-ins for the built files: no compiler runs, the tree is not touched"""
     import shutil

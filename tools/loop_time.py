@@ -1,6 +1,5 @@
 """GPU: ms per DDPM step of the hipGraph loop (B=64, T=196 by default), repeated: loop_time.py [prec] [B] [ddpm_steps] [reps] [tuning] [T] [nograph]
-(tuning = tamf_set_gemm_tuning value the graph is captured under, e.g. 0x400fffff; "nograph" = plain launches - what the overlap probe,
-selection bit 256 = tuning 0x100fffff of a -DTAMF_BENCH build, needs)"""
+(tuning = tamf_set_gemm_tuning value the graph is captured under, e.g. 0x400fffff; "nograph" = plain launches)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "oakink2-tamf_amd")]
