@@ -62,6 +62,9 @@ int tamf_mano_model_set_tiles(tamf_mano_model* model, int32_t m_tiles);
 /* The layer's forward (SMPL eq. 2-4 with the blend shapes of eq. 8-9; joints as described above), enqueued on `stream`:
  *   quat (N,16,4) f32 device, (w,x,y,z), normalised here as q / max(|q|, 1e-12); 16-byte aligned      betas (N,10) f32 device
  *   verts_out (N,V,3) f32 device          joints_out (N,21,3) f32 device, or NULL
+ * The quaternions may have any length whose square float32 holds: |q| up to 1.8e19 (sqrt of FLT_MAX) is in the contract and a zero
+ * quaternion is the identity rotation; above that the float32 norm overflows, the joint gets the identity rotation -
+ * outside the contract, as are non-finite inputs (which spoil the outputs of their own frame only).
  * fp32 throughout; the blend-shape contraction runs on v_mfma_f32_16x16x4_f32 in a fixed K order.  A frame's output bits depend
  * on its own inputs and the model only - not on N, on its position in the batch or on the launch.  N = 0 launches nothing; N < 0 or
  * a null pointer is TAMF_ERR_INVALID.  Does not synchronise. */

@@ -37,14 +37,18 @@ static bool all_finite(const double* p, size_t n) {
 extern "C" int tamf_mano_model_create(int32_t V, const double* v_template, const double* shapedirs, const double* posedirs,
                                       const double* J_regressor, const double* weights, const int32_t* parents, const int32_t* tip_ids,
                                       const int32_t* joint_order, int32_t center_idx, tamf_mano_model** model_out) {
-  if (!v_template || !shapedirs || !posedirs || !J_regressor || !weights || !parents || !model_out) return fail(TAMF_ERR_INVALID, "null argument");
-  *model_out = nullptr;
+  if (!model_out) return fail(TAMF_ERR_INVALID, "model_out is null");
+  *model_out = nullptr;  // (on every failure below, a null mandatory pointer included)
+  const struct { const char* name; const double* p; size_t per_vertex; } arr[5] = {
+      {"v_template", v_template, 3}, {"shapedirs", shapedirs, 3 * MANO_NB}, {"posedirs", posedirs, 3 * MANO_NP},
+      {"J_regressor", J_regressor, MANO_J}, {"weights", weights, MANO_J}};
+  for (const auto& x : arr)
+    if (!x.p) return fail(TAMF_ERR_INVALID, std::string(x.name) + " is null");
+  if (!parents) return fail(TAMF_ERR_INVALID, "parents is null");
   if (V < 1 || V > MANO_VMAX) return fail(TAMF_ERR_INVALID, "V = " + std::to_string(V) + " outside [1, 1024]");
   if (center_idx < -1 || center_idx >= MANO_NJ) return fail(TAMF_ERR_INVALID, "center_idx = " + std::to_string(center_idx) + " outside [-1, 21)");
-  const size_t v = (size_t)V;
-  if (!all_finite(v_template, v * 3) || !all_finite(shapedirs, v * 3 * MANO_NB) || !all_finite(posedirs, v * 3 * MANO_NP) ||
-      !all_finite(J_regressor, v * MANO_J) || !all_finite(weights, v * MANO_J))
-    return fail(TAMF_ERR_INVALID, "a model array holds a non-finite value");
+  for (const auto& x : arr)
+    if (!all_finite(x.p, (size_t)V * x.per_vertex)) return fail(TAMF_ERR_INVALID, std::string(x.name) + " holds a non-finite value");
   int tab[MANO_T_INTS];
   int maxdepth = 0;
   for (int j = 0; j < MANO_J; ++j) {

@@ -184,6 +184,11 @@ def _check(lib, rc: int) -> None:
         raise RuntimeError(f"libtamf_mano: {lib.tamf_mano_last_error().decode()} (status {rc})")
 
 
+def _aligned16(t):
+    """the kernels read a frame's quaternions as float4: a contiguous view that starts off a 16-byte boundary is copied"""
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 _function = None
 
 
@@ -302,6 +307,7 @@ class HipManoLayer:
         from .hip_backend import _stream_ptr
 
         N, V = int(q.shape[0]), self.arrays.n_verts
+        q = _aligned16(q)
         verts = torch.empty((N, V, 3), dtype=torch.float32, device=self.device)
         joints = torch.empty((N, N_OUT_JOINTS, 3), dtype=torch.float32, device=self.device) if with_joints else None
         if N > 0:
@@ -331,7 +337,7 @@ class HipManoLayer:
                 raise ValueError(f"{name}: expected {shape}, got {tuple(t.shape)}")
             return t.detach().to(device=self.device, dtype=torch.float32).contiguous()
 
-        q, b = f32(pose_coeffs, (N, N_JOINTS, 4), "pose_coeffs"), f32(betas, (N, N_BETAS), "betas")
+        q, b = _aligned16(f32(pose_coeffs, (N, N_JOINTS, 4), "pose_coeffs")), f32(betas, (N, N_BETAS), "betas")
         dv, dj = f32(dverts, (N, V, 3), "dverts"), f32(djoints, (N, N_OUT_JOINTS, 3), "djoints")
         dq = torch.empty((N, N_JOINTS, 4), dtype=torch.float32, device=self.device)
         db = torch.empty((N, N_BETAS), dtype=torch.float32, device=self.device) if want_dbetas else None
