@@ -1,7 +1,7 @@
 // The test and measurement entry points of libtamf_hip_hooks.so (include/tamf_hip_test.h) and everything that only they use: the
 // tail of tamf_hip.hip in the -DTAMF_TEST_HOOKS build, included there once and nowhere else.  The product library does not parse
 // this file.  What the hooks SET but product code reads (the guard-band and allocation-failure state of dev_alloc, the selection words
-// g_krot / g_sel, the list of live contexts, the launch lock) is defined in tamf_hip.hip.
+// g_krot / g_sel in tamf_launch.h, the list of live contexts, the launch lock) is defined in tamf_hip.hip and its headers.
 #pragma once
 #include "../../include/tamf_hip_test.h"
 
@@ -95,20 +95,19 @@ static int test_gemm_impl(int M, int N, int K, const float* a, const float* w, c
     EpiResid<Op> ep{bias, gamma, c, Op::PREC == 0 ? nullptr : yo, N, stats_out, ACT_NONE, {}, LnStats{stats_in, N / 32, 1.0f / (float)N, 1e-5f}};
     // (the selection of the step: launch_resid for clip-aligned M - small tiles with the deep K pipeline when there are few of them - and
     // for every other M the small tiles where they fit, so that ragged tile edges of that kernel are tested too, else 128 x 128)
-    const int sp = M % 208 == 0 ? 208 : (M % 168 == 0 ? 168 : 0);
-    if (sp) e = launch_resid<Op>(ga, ep, M / sp, sp, st);
-    else if (!small_m_launch<Op>(ga, ep, st, &e)) e = gemm128<Op>(ga, ep, st);
+    const int sp = clip_rows_of_m(M);
+    e = sp ? launch_resid<Op>(ga, ep, M / sp, sp, st) : launch_rows<Op>(ga, ep, st);
   } else {
     EpiStoreF32 ep{bias, c, N, act};
-    // M = n * 208 rows (T = 196) or n * 168 rows (T = 160): the clip-aligned tiles the encoder layers use (same selection as
-    // enqueue_step; 32 clips or fewer: the row-part tiles)
+    // M = n * 208 rows (T = 196) or n * 168 rows (T = 160): the clip-aligned tiles the encoder layers use (a ladder of this hook's
+    // own - the step has no plain fp32 store; 32 clips or fewer: the row-part tiles)
     const int nc = M / 208;
     bool done = false;
     if (M % 208 == 0 && N % 256 == 0 && ClipLaunch<Op, 4, EpiStoreF32>::applies(nc, 208, N, Kp)) {
       e = ClipLaunch<Op, 4, EpiStoreF32>::launch(nullptr, ao, Kp, wo, Kp, nc, 208, N, Kp, ep, st);
       done = true;
     } else {
-      const int sp = M % 208 == 0 ? 208 : (M % 168 == 0 ? 168 : 0);
+      const int sp = clip_rows_of_m(M);
       if (sp) {
         TAMF_CLIP_NSUB(sp, {
           if (ClipLaunch<Op, 2, EpiStoreF32, NSP, 2>::applies_parts(M / sp, sp, N, Kp)) {
@@ -247,16 +246,14 @@ static int bench_gemm_impl(int epi_kind, int M, int N, int K, int iters, float* 
         const LnStats ln{(const float2*)x, K / 32, 1.0f / (float)K, 1e-5f};  // (any finite numbers: x is M x N >= M x K / 16 floats)
         if (epi_kind == 10) {
           EpiBiasAct<Op, true> ep{vec, nullptr, 0, o, N, ACT_GELU, {}, ln};
-          if (M % 208 == 0 && ClipLaunch<Op, 4, EpiBiasAct<Op, true>>::applies(M / 208, 208, N, K))
-            e = ClipLaunch<Op, 4, EpiBiasAct<Op, true>>::launch(nullptr, a, K, w, K, M / 208, 208, N, K, ep, st);
-          else e = gemm128<Op>(ga, ep, st);
+          e = clip_rows_of_m(M) == 208 ? launch_ffn1<Op>(ga, ep, M / 208, 208, st) : gemm128<Op>(ga, ep, st);
         } else if (epi_kind == 11) {
           const int d = N / 3;
           EpiQKV<Op, true> ep{vec, o, o2, d, d / 128, 128, 208, 224, 0.1f, {}, ln};
           e = gemm128<Op>(ga, ep, st);
         } else {
           EpiResid<Op> ep{vec, vec + N, x, o, N, (float2*)o2, ACT_NONE, {}, LnStats{nullptr, N / 32, 1.0f / (float)N, 1e-5f}};
-          e = M % 208 == 0 ? launch_resid<Op>(ga, ep, M / 208, 208, st) : gemm128<Op>(ga, ep, st);
+          e = clip_rows_of_m(M) == 208 ? launch_resid<Op>(ga, ep, M / 208, 208, st) : gemm128<Op>(ga, ep, st);
         }
       }
     } else {

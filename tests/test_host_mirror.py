@@ -111,6 +111,76 @@ def test_hooks_are_compiled_through_one_guard():
         assert re.search(r'^extern "C" int %s\(' % sym, hooks, flags=re.M) and not re.search(r'^extern "C" int %s\(' % sym, "\n".join(lines), flags=re.M)
 
 
+def _csrc(name):
+    from oakink2_tamf_amd import _lib
+
+    return open(os.path.join(_lib.CSRC, name)).read()
+
+
+def _function_text(src, signature):
+    """the text of a function of `src` from `signature` to the brace that closes its body"""
+    start = src.index(signature)
+    depth, i = 0, src.index("{", start)
+    while True:
+        depth += {"{": 1, "}": -1}.get(src[i], 0)
+        i += 1
+        if depth == 0:
+            return src[start:i]
+
+
+def test_launch_selection_is_in_one_header():
+    """csrc/tamf_launch.h decides every GEMM / attention launch: the step names its GEMMs and no launcher, one place sets the dynamic-LDS
+    attribute, one function knows the clip lengths that have clip tiles"""
+    from oakink2_tamf_amd import _lib
+
+    assert "tamf_launch.h" in _lib.SAMPLER.sources
+    step = _function_text(_csrc("tamf_hip.hip"), "static int enqueue_step(")
+    assert step.rstrip().endswith("return 0;\n}") and "gemm_head_ddpm" in step  # (the whole body)
+    for word in ("ClipLaunch<", "GemmLaunch<", "GemmDeepLaunch<", "TAMF_CLIP_NSUB"):
+        assert word not in step, word
+    three = {n: _csrc(n) for n in ("tamf_hip.hip", "tamf_launch.h", "tamf_hip_hooks.h")}
+    assert sum(t.count("hipFuncAttributeMaxDynamicSharedMemorySize") for t in three.values()) == 1
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in _function_text(three["tamf_launch.h"], "static hipError_t lds_once(")
+    # 176 as a bound of a clip length: a comparison of something named Sp / Sp_ / sp with it, in either order
+    bound = re.compile(r"\b[Ss]p_?\)?\s*(?:<=|>=|<|>|==)\s*\(?176\b|\b176\)?\s*(?:<=|>=|<|>|==)\s*\(?[Ss]p_?\b")
+    table = _function_text(three["tamf_launch.h"], "static inline int clip_tile_rows(int Sp)")
+    assert len(bound.findall(table)) == 2  # (176, 208] and (144, 176]
+    for name, text in three.items():
+        assert not bound.findall(text.replace(table, "")), name
+
+
+def test_clip_length_table_and_vt_row_keys(tmp_path):
+    """clip_tile_rows and vt_row_keys (csrc/tamf_launch.h) compiled on their own, as the plain host functions they are: the table against
+    the ranges written out here, and a V^T row that holds both the sequence and every row of the clip tile that writes it, in whole
+    32-key blocks"""
+    import shutil
+    import subprocess
+
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    hdr = _csrc("tamf_launch.h")
+    main = r"""
+#include <cstdio>
+%s
+%s
+int main() {
+  for (int Sp = 8; Sp <= 224; Sp += 8) printf("t %%d %%d\n", Sp, clip_tile_rows(Sp));
+  for (int S = 1; S <= 224; ++S) printf("k %%d %%d\n", S, vt_row_keys(S, (S + 7) / 8 * 8));
+  return 0;
+}
+""" % (_function_text(hdr, "static inline int clip_tile_rows(int Sp)"), _function_text(hdr, "static inline int vt_row_keys(int S, int Sp)"))
+    (tmp_path / "m.cpp").write_text(main)
+    subprocess.run([cxx, "-std=c++17", "-O0", "-o", str(tmp_path / "m"), str(tmp_path / "m.cpp")], check=True)
+    out = subprocess.run([str(tmp_path / "m")], check=True, capture_output=True, text=True).stdout.split("\n")
+    rows = {int(l.split()[1]): int(l.split()[2]) for l in out if l.startswith("t ")}
+    keys = {int(l.split()[1]): int(l.split()[2]) for l in out if l.startswith("k ")}
+    assert sorted(rows) == list(range(8, 225, 8)) and sorted(keys) == list(range(1, 225))
+    for Sp, tile in rows.items():
+        assert tile == (208 if Sp in (184, 192, 200, 208) else 176 if Sp in (152, 160, 168, 176) else 0), Sp
+    for S, k in keys.items():
+        assert k % 32 == 0 and k >= max(S, rows[(S + 7) // 8 * 8]) and k < max(S, rows[(S + 7) // 8 * 8]) + 32, S
+
+
 def test_the_sampler_has_five_build_switches():
     """the TAMF_ identifiers that a preprocessor conditional of the sampler's sources tests (#if / #ifdef / #ifndef / #elif, defined(...)
     included) are the hooks build, the fallback of the counted waits and the three instruments of tools/ - a decided A/B knob is plain code"""
