@@ -2,15 +2,8 @@
 // workspace and the launch sequence of the kernels of tamf_encoder_grad.h.  Host conventions of tamf_weights.h: an int status, a
 // thread-local last-error string, nothing thrown across the ABI.
 //
-// Workspace (floats; R = max_batch * (max_frames + 4) token rows, BT = max_batch * max_frames frame rows), kept from the forward for
-// the backward:
-//   input stage   shm [B][sd], oem [B][od], trm [BT][qd] (means over frames / objects), cat [BT][128] (hand | object embedding),
-//                 zpre, z [BT][64] (input_merge.0 before / after SiLU), pre [R][64] (token rows before nan_to_num and PE)
-//   per layer     x [R][64] (its input; x[L] is the output), qkv [R][192], stat [B][4][S][2] (softmax max, sum), att [R][64],
-//                 x1pre, x1, x2pre [R][64] (LayerNorm inputs / output), hpre, gel [R][ff] (linear1 output, dropped-out GELU)
-//   head          h1pre, h1, h2pre, h2 [B][64]
-// and the transient gradients of the backward (dx, dz, dym, tt, dx1, datt [R][64], dqkv [R][192], dh [R][ff], delta, dpre, dzin, dcat,
-// dact, dh1, dh2, the per-clip losses) and the slab of weight-gradient partial sums [<= 64 splits][N][K + 1].
+// Row counts of the workspace structs below: R = B (T + 4) token rows (3 prefix rows, T frames, the classification row of every clip),
+// BT = B T frame rows; the context carves them for (max_batch, max_frames), a step addresses them with its own B and T.
 #include "tamf_weights.h"
 
 #include "../../include/tamf_enctrain.h"
@@ -18,7 +11,7 @@
 
 namespace {
 
-constexpr int MAX_SPLIT = 64, SPLIT_ROWS = 128;
+constexpr int MAX_SPLIT = 64, SPLIT_ROWS = 128, D = ENC_D;
 
 struct Bound {
   std::vector<int64_t> shape;
@@ -26,131 +19,358 @@ struct Bound {
   const float* p = nullptr;
   float* g = nullptr;
 };
-
-struct LayerWs {
-  long x, qkv, stat, att, x1pre, x1, x2pre, hpre, gel;
-};
-
-// one bound (weight, bias) pair with its gradients - a linear map, or the gain and bias of a LayerNorm
+// one declared (weight, bias) pair, N x K and N, where it is bound - a linear map, or the gain and bias of a LayerNorm (K = 0)
 struct Lin {
-  const float *w = nullptr, *b = nullptr;
-  float *gw = nullptr, *gb = nullptr;
+  const Bound *w = nullptr, *b = nullptr;
+  int N = 0, K = 0;
 };
 struct LayerP {
   Lin inproj, out, l1, l2, n1, n2;
 };
+
+struct Dims {
+  long B, BT, R;
+  int F, ff, sd, od, qd;
+};
+Dims dims(const tamf_arch& a, long B, long T) {
+  return {B, B * T, B * (T + ENC_P + 1), a.input_dim, a.ff_size, a.hand_shape_dim, a.obj_embed_dim, a.obj_input_dim};
+}
+
+// ---- the workspace (offsets in floats): what the forward keeps for the backward, then the backward's own buffers ----
+struct InputWs {
+  long shm, oem, trm, cat, zpre, z, pre;
+};
+InputWs carve_input(Carver& cv, const Dims& n) {
+  InputWs x;
+  x.shm = cv.take(n.B * n.sd);            // [B][sd]    the hand shape, mean over the frames
+  x.oem = cv.take(n.B * n.od);            // [B][od]    the object embedding, mean over the objects
+  x.trm = cv.take(n.BT * n.qd);           // [BT][qd]   the object trajectory, mean over the objects
+  x.cat = cv.take(n.BT * 2 * D);          // [BT][128]  pose embedding | trajectory embedding
+  x.zpre = cv.take(n.BT * D);             // [BT][64]   the first merge map before ...
+  x.z = cv.take(n.BT * D);                //            ... and after SiLU
+  x.pre = cv.take(n.R * D);               // [R][64]    token rows before nan_to_num and PE
+  return x;
+}
+struct LayerWs {
+  long x, qkv, stat, att, x1pre, x1, x2pre, hpre, gel;
+};
+LayerWs carve_layer(Carver& cv, const Dims& n) {
+  LayerWs x;
+  x.x = cv.take(n.R * D);                 // [R][64]       the layer's input
+  x.qkv = cv.take(n.R * 3 * D);           // [R][192]
+  x.stat = cv.take(n.R * EG_H * 2);       // [B][4][S][2]  softmax (max, sum)
+  x.att = cv.take(n.R * D);               // [R][64]       attention output
+  x.x1pre = cv.take(n.R * D);             // [R][64]       LayerNorm 1: input,
+  x.x1 = cv.take(n.R * D);                //               output
+  x.x2pre = cv.take(n.R * D);             // [R][64]       LayerNorm 2: input (its output is the next layer's x)
+  x.hpre = cv.take(n.R * n.ff);           // [R][ff]       the feed-forward hidden rows before GELU,
+  x.gel = cv.take(n.R * n.ff);            //               after GELU and dropout
+  return x;
+}
+struct HeadWs {
+  long xlast, h1pre, h1, h2pre, h2;
+};
+HeadWs carve_head(Carver& cv, const Dims& n) {
+  HeadWs x;
+  x.xlast = cv.take(n.R * D);             // [R][64]  the last layer's output
+  x.h1pre = cv.take(n.B * D);             // [B][64]  the output head's two hidden rows, each before ...
+  x.h1 = cv.take(n.B * D);                //          ... and after SiLU
+  x.h2pre = cv.take(n.B * D);
+  x.h2 = cv.take(n.B * D);
+  return x;
+}
+struct GradWs {
+  long dx, dz, dym, tt, dx1, datt, dqkv, dh, delta, dpre, dzin, dcat, dact, dh1, dh2, lb, slab;
+};
+GradWs carve_grads(Carver& cv, const Dims& n, long slab_nk) {
+  GradWs x;
+  x.dx = cv.take(n.R * D);                // [R][64] each: the gradient of a layer's output / input,
+  x.dz = cv.take(n.R * D);                //   of a LayerNorm's input,
+  x.dym = cv.take(n.R * D);               //   of the linear output under that LayerNorm's residual dropout,
+  x.tt = cv.take(n.R * D);                //   dy * xhat (the gain gradient before the column sum),
+  x.dx1 = cv.take(n.R * D);               //   of LayerNorm 1's output,
+  x.datt = cv.take(n.R * D);              //   of the attention output
+  x.dqkv = cv.take(n.R * 3 * D);          // [R][192]
+  x.dh = cv.take(n.R * n.ff);             // [R][ff]
+  x.delta = cv.take(n.R * EG_H);          // [B][4][S]  sum_k P dP of every query
+  x.dpre = cv.take(n.R * D);              // [R][64]    of InputWs::pre,
+  x.dzin = cv.take(n.BT * D);             // [BT][64]   zpre,
+  x.dcat = cv.take(n.BT * 2 * D);         // [BT][128]  cat
+  x.dact = cv.take(n.B * n.F);            // [B][F]     of the activation,
+  x.dh1 = cv.take(n.B * D);               // [B][64]    HeadWs::h1pre,
+  x.dh2 = cv.take(n.B * D);               //            h2pre
+  x.lb = cv.take(n.B);                    // [B]        the per-clip losses
+  x.slab = cv.take(slab_nk * MAX_SPLIT);  // [<= 64 splits][N][K + 1] weight-gradient partial sums of the largest linear map
+  return x;
+}
 
 }  // namespace
 
 struct tamf_enctrain_ctx {
   tamf_arch arch;
   int maxB, maxT, device;
-  std::vector<std::string> order;
-  std::map<std::string, Bound> t;
-  float* ws = nullptr;
-  int* cnt = nullptr;           // [maxB]
-  long long* clip = nullptr;    // [maxB]
-  // offsets in floats
-  long shm, oem, trm, cat, zpre, z, pre, xlast, h1pre, h1, h2pre, h2;
-  long dx, dz, dym, tt, dx1, datt, dqkv, dh, delta, dpre, dzin, dcat, dact, dh1, dh2, lb, slab;
-  std::vector<LayerWs> lw;
-  // the bound pointers, looked up once after a bind (resolve()), not per launch
-  bool resolved = false;
-  const float *rh = nullptr, *lh = nullptr, *cls = nullptr, *pe = nullptr;
+  std::map<std::string, Bound> t;                                      // (nodes are address-stable: Lin points into them)
+  std::vector<const std::pair<const std::string, Bound>*> order;       // in declaration order
+  long slab_nk = 0;                                                    // the largest N (K + 1) of a declared linear map
+  const Bound *rh, *lh, *cls, *pe;
   Lin shape, obj, pose, traj, m0, m2, p0, p2, p4;
   std::vector<LayerP> lp;
+  float* ws = nullptr;
+  int* cnt = nullptr;         // [maxB]
+  long long* clip = nullptr;  // [maxB]
+  InputWs in;
+  std::vector<LayerWs> lw;
+  HeadWs head;
+  GradWs g;
 };
 
 namespace {
 
-void declare(tamf_enctrain_ctx* c, const std::string& k, std::vector<int64_t> shape, bool trainable = true) {
-  c->order.push_back(k);
-  Bound& b = c->t[k];
-  b.shape = std::move(shape);
-  b.trainable = trainable;
+const Bound* declare(tamf_enctrain_ctx* c, const std::string& k, std::vector<int64_t> shape, bool trainable = true) {
+  auto it = c->t.emplace(k, Bound{std::move(shape), trainable}).first;
+  c->order.push_back(&*it);
+  return &it->second;
 }
-void declare_linear(tamf_enctrain_ctx* c, const std::string& k, int64_t o, int64_t i) {
-  declare(c, k + ".weight", {o, i});
-  declare(c, k + ".bias", {o});
+Lin declare_pair(tamf_enctrain_ctx* c, const std::string& wk, const std::string& bk, int o, int i) {
+  c->slab_nk = std::max(c->slab_nk, (long)o * (i + 1));
+  const Bound* w = declare(c, wk, {o, i});
+  return Lin{w, declare(c, bk, {o}), o, i};
 }
-
-Lin lin_of(tamf_enctrain_ctx* c, const std::string& wk, const std::string& bk) {
-  const Bound &w = c->t.at(wk), &b = c->t.at(bk);
-  Lin l;
-  l.w = w.p;
-  l.b = b.p;
-  l.gw = w.g;
-  l.gb = b.g;
-  return l;
+Lin declare_linear(tamf_enctrain_ctx* c, const std::string& k, int o, int i) { return declare_pair(c, k + ".weight", k + ".bias", o, i); }
+Lin declare_norm(tamf_enctrain_ctx* c, const std::string& k) {
+  const Bound* w = declare(c, k + ".weight", {D});
+  return Lin{w, declare(c, k + ".bias", {D}), D, 0};
 }
-Lin lin_of(tamf_enctrain_ctx* c, const std::string& k) { return lin_of(c, k + ".weight", k + ".bias"); }
-void resolve(tamf_enctrain_ctx* c) {
-  c->rh = c->t.at("hand_side_process.rh_embed").p;
-  c->lh = c->t.at("hand_side_process.lh_embed").p;
-  c->cls = c->t.at("classification_token").p;
-  c->pe = c->t.at("sequence_pos_encoder.pe").p;
-  c->shape = lin_of(c, "hand_shape_process.shape_embed");
-  c->obj = lin_of(c, "obj_embed_process.embedding");
-  c->pose = lin_of(c, "input_process.poseEmbedding");
-  c->traj = lin_of(c, "obj_input_process.poseEmbedding");
-  c->m0 = lin_of(c, "input_merge.0");
-  c->m2 = lin_of(c, "input_merge.2");
-  c->p0 = lin_of(c, "output_process.poseFinal.0");
-  c->p2 = lin_of(c, "output_process.poseFinal.2");
-  c->p4 = lin_of(c, "output_process.poseFinal.4");
-  c->lp.resize(c->arch.num_layers);
-  for (int l = 0; l < c->arch.num_layers; ++l) {
+// every tensor of the state dict, in its order
+void declare_model(tamf_enctrain_ctx* c) {
+  const tamf_arch& a = c->arch;
+  c->rh = declare(c, "hand_side_process.rh_embed", {D}, false);
+  c->lh = declare(c, "hand_side_process.lh_embed", {D}, false);
+  c->shape = declare_linear(c, "hand_shape_process.shape_embed", D, a.hand_shape_dim);
+  c->obj = declare_linear(c, "obj_embed_process.embedding", D, a.obj_embed_dim);
+  c->cls = declare(c, "classification_token", {1, 1, D}, false);
+  c->pose = declare_linear(c, "input_process.poseEmbedding", D, a.input_dim);
+  c->traj = declare_linear(c, "obj_input_process.poseEmbedding", D, a.obj_input_dim);
+  c->m0 = declare_linear(c, "input_merge.0", D, 2 * D);
+  c->m2 = declare_linear(c, "input_merge.2", D, D);
+  c->pe = declare(c, "sequence_pos_encoder.pe", {5000, 1, D}, false);
+  c->lp.resize(a.num_layers);
+  for (int l = 0; l < a.num_layers; ++l) {
     const std::string p = "seqTransEncoder.layers." + std::to_string(l) + ".";
     LayerP& x = c->lp[l];
-    x.inproj = lin_of(c, p + "self_attn.in_proj_weight", p + "self_attn.in_proj_bias");
-    x.out = lin_of(c, p + "self_attn.out_proj");
-    x.l1 = lin_of(c, p + "linear1");
-    x.l2 = lin_of(c, p + "linear2");
-    x.n1 = lin_of(c, p + "norm1");
-    x.n2 = lin_of(c, p + "norm2");
+    x.inproj = declare_pair(c, p + "self_attn.in_proj_weight", p + "self_attn.in_proj_bias", 3 * D, D);
+    x.out = declare_linear(c, p + "self_attn.out_proj", D, D);
+    x.l1 = declare_linear(c, p + "linear1", a.ff_size, D);
+    x.l2 = declare_linear(c, p + "linear2", D, a.ff_size);
+    x.n1 = declare_norm(c, p + "norm1");
+    x.n2 = declare_norm(c, p + "norm2");
   }
-  c->resolved = true;
+  c->p0 = declare_linear(c, "output_process.poseFinal.0", D, D);
+  c->p2 = declare_linear(c, "output_process.poseFinal.2", D, D);
+  c->p4 = declare_linear(c, "output_process.poseFinal.4", a.input_dim, D);
+}
+
+Drop make_drop(uint64_t seed, uint32_t step, float p, const long long* clip) {
+  Drop d;
+  d.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
+  d.k1 = (uint32_t)(seed >> 32);
+  d.step = step;
+  d.thr = (uint32_t)std::min(4294967295.0, std::floor((double)p * 4294967296.0));
+  d.scale = 1.0f / (1.0f - p);
+  d.clip = clip;
+  return d;
 }
 
 RowMap flat(long ld) { return RowMap{1 << 30, 0, ld}; }
 
+// the epilogue of a lin_kernel launch: an EgMode with the operands that mode reads
+struct Epi {
+  int mode = EG_LIN;
+  float* C2 = nullptr;
+  const float* R = nullptr;
+  int site = 0, q0 = 0, rq0 = 0;
+};
+Epi silu(float* pre) { return {EG_SILU, pre}; }
+Epi gelu_drop(float* pre, int site, int q0) { return {EG_GELU_DROP, pre, nullptr, site, q0}; }
+Epi drop_res(const float* res, int site, int q0) { return {EG_DROP_RES, nullptr, res, site, q0}; }
+Epi bwd_silu(const float* pre) { return {EG_BWD_SILU, nullptr, pre}; }
+Epi bwd_gelu_drop(const float* pre, int site, int q0) { return {EG_BWD_GELU_DROP, nullptr, pre, site, q0}; }
+Epi bwd_res(const float* res) { return {EG_BWD_RES, nullptr, res}; }
+Epi bwd_res_q0(const float* res, int rq0) { return {EG_BWD_RES_Q0, nullptr, res, 0, 0, rq0}; }
+
+// the caller's tensors of one step (device memory; cnt is the context's copy of obj_num or null)
+struct Batch {
+  const float *pose, *shape, *oemb, *traj;
+  const uint8_t* side;
+  const int* cnt;
+  const long long* labels;
+  float *loss, *act;
+  int nobj;
+};
+
+// the rows a layer computes: all S of every clip, or - the last layer - the classification row alone (K and V of every row)
+struct LayerView {
+  int q0, nq, M, site;  // first row and rows per clip, rows in all, the layer's first dropout site
+  RowMap r64, rff;      // those rows inside [B][S][64] and [B][S][ff],
+  long o64, off;        // from these offsets
+};
+
 struct Step {
-  tamf_enctrain_ctx* c;
-  hipStream_t st;
-  int B, T, S;
-  Drop d;
+  tamf_enctrain_ctx* c = nullptr;
+  hipStream_t st = nullptr;
+  Dims n{};
+  int B = 0, T = 0, S = 0;
+  Batch io{};
+  Drop drop{};
   hipError_t err = hipSuccess;
 
   float* w(long off) const { return c->ws + off; }
+  float* xof(int l) const { return w(l < (int)c->lw.size() ? c->lw[l].x : c->head.xlast); }  // layer l's input; xof(L): the output
   RowMap rows(int nq, long ld) const { return RowMap{nq, (long)S * ld, ld}; }  // nq rows of every clip inside [B][S][ld]
-  void check() {
-    if (err == hipSuccess) err = hipGetLastError();
+  RowMap one() const { return rows(1, D); }
+  RowMap frames() const { return rows(T, D); }
+  float* cls_rows() const { return xof((int)c->lw.size()) + (long)(S - 1) * D; }  // the encoder's classification rows, at one()
+  size_t att_lds() const { return (size_t)S * ENC_HD * 2 * sizeof(float); }
+  LayerView layer_view(int l) const {
+    const int q0 = l == (int)c->lw.size() - 1 ? S - 1 : 0, nq = S - q0;
+    return {q0, nq, B * nq, 1 + 4 * l, rows(nq, D), rows(nq, n.ff), (long)q0 * D, (long)q0 * n.ff};
   }
 
-  void lin(LinArgs a) {
-    a.d = d;
-    const long tiles = (long)((a.M + 15) / 16) * ((a.N + 15) / 16);
-    lin_kernel<<<blocks(tiles, 4), 256, 0, st>>>(a);
-    check();
+  // every launch of the library: the first launch error is kept
+  template <class K, class... A>
+  void launch(K kernel, dim3 grid, int block, size_t lds, A... args) {
+    kernel<<<grid, block, lds, st>>>(args...);
+    if (err == hipSuccess) err = hipGetLastError();
   }
-  // dW (N, K) and db (N) of a linear map from its output gradient Y and its input A over R rows
-  void wgrad(const float* Y, RowMap ym, const float* A, RowMap am, int R, int N, int K, const Lin& lin) {
-    const int nsplit = std::max(1, std::min(MAX_SPLIT, (R + SPLIT_ROWS - 1) / SPLIT_ROWS));
+  int status() const { return err == hipSuccess ? 0 : fail(TAMF_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(err)); }
+
+  void lin(LinArgs a, const Epi& e) {
+    a.rm = a.cm;
+    a.mode = e.mode;
+    a.C2 = e.C2;
+    a.R = e.R;
+    a.site = e.site;
+    a.q0 = e.q0;
+    a.rq0 = e.rq0;
+    a.d = drop;
+    launch(lin_kernel, blocks((long)((a.M + 15) / 16) * ((a.N + 15) / 16), 4), 256, 0, a);
+  }
+  // C (M, N) = epilogue(A (M, K) . W^T + b) of a linear map
+  void fwd(const Lin& l, const float* A, RowMap am, float* C, RowMap cm, int M, const Epi& e = {}) {
+    LinArgs a{};
+    a.A = A, a.am = am, a.W = l.w->p, a.swn = l.K, a.swk = 1, a.bias = l.b->p, a.C = C, a.cm = cm, a.M = M, a.N = l.N, a.K = l.K;
+    lin(a, e);
+  }
+  // the data gradient of the same map: dA (M, K) = epilogue(dY (M, N) . W)
+  void dgrad(const Lin& l, const float* dY, RowMap ym, float* dA, RowMap cm, int M, const Epi& e = {}) {
+    LinArgs a{};
+    a.A = dY, a.am = ym, a.W = l.w->p, a.swn = 1, a.swk = l.K, a.C = dA, a.cm = cm, a.M = M, a.N = l.K, a.K = l.N;
+    lin(a, e);
+  }
+  // its weight and bias gradients from its output gradient Y and its input A over R rows
+  void wgrad(const Lin& l, const float* Y, RowMap ym, const float* A, RowMap am, int R) {
+    const int N = l.N, K = l.K, nsplit = std::max(1, std::min(MAX_SPLIT, (R + SPLIT_ROWS - 1) / SPLIT_ROWS));
     const int chunk = ((R + nsplit - 1) / nsplit + 3) / 4 * 4;
-    WgradArgs a{Y, ym, A, am, w(c->slab), R, N, K, nsplit, chunk};
     const long tiles = (long)((N + 15) / 16) * ((K + 1 + 15) / 16) * nsplit;
-    wgrad_kernel<<<blocks(tiles, 4), 256, 0, st>>>(a);
-    check();
-    reduce_kernel<<<blocks((long)N * (K + 1), 256), 256, 0, st>>>(w(c->slab), nsplit, N, K + 1, K, lin.gw, lin.gb);
-    check();
+    launch(wgrad_kernel, blocks(tiles, 4), 256, 0, WgradArgs{Y, ym, A, am, w(c->g.slab), R, N, K, nsplit, chunk});
+    launch(reduce_kernel, blocks((long)N * (K + 1), 256), 256, 0, w(c->g.slab), nsplit, N, K + 1, K, l.w->g, l.b->g);
   }
   void colsum(const float* X, RowMap xm, int R, float* out) {
     const int nsplit = std::max(1, std::min(MAX_SPLIT, (R + SPLIT_ROWS - 1) / SPLIT_ROWS));
-    const int chunk = (R + nsplit - 1) / nsplit;
-    colsum_kernel<<<nsplit, ENC_D, 0, st>>>(X, xm, R, chunk, w(c->slab));
-    check();
-    reduce_kernel<<<1, ENC_D, 0, st>>>(w(c->slab), nsplit, 1, ENC_D, ENC_D, out, nullptr);
-    check();
+    launch(colsum_kernel, nsplit, D, 0, X, xm, R, (R + nsplit - 1) / nsplit, w(c->g.slab));
+    launch(reduce_kernel, 1, D, 0, w(c->g.slab), nsplit, 1, D, D, out, nullptr);
+  }
+  void ln_fwd(const LayerView& v, const float* X, float* Y, const Lin& norm) {
+    launch(ln_fwd_kernel, blocks(v.M, 4), 256, 0, X, v.r64, Y, v.r64, norm.w->p, norm.b->p, v.M);
+  }
+  // LayerNorm backward over the view's rows of dy (offsets): dz, dym = dz under the dropout of `site`, the gain and bias gradients
+  void ln_bwd(const LayerView& v, long dy, long pre, const Lin& norm, int site) {
+    const GradWs& g = c->g;
+    const long o = v.o64;
+    launch(ln_bwd_kernel, blocks(v.M, 4), 256, 0, w(dy) + o, w(pre) + o, v.r64, norm.w->p, w(g.dz) + o, w(g.dym) + o, w(g.tt) + o, v.M, v.q0, site, drop);
+    colsum(w(g.tt) + o, v.r64, v.M, norm.w->g);
+    colsum(w(dy) + o, v.r64, v.M, norm.b->g);
+  }
+
+  void forward_input() {
+    const InputWs& x = c->in;
+    const PrepArgs a{io.shape, io.oemb, io.traj, io.side, io.cnt, c->rh->p, c->lh->p, c->cls->p, w(x.shm), w(x.oem), w(x.trm), w(x.pre),
+                     B, T, io.nobj, n.sd, n.od, n.qd};
+    launch(prep_kernel, blocks(n.B * n.sd + n.B * n.od + n.BT * n.qd + n.B * 2 * D, 256), 256, 0, a);
+    fwd(c->shape, w(x.shm), flat(n.sd), w(x.pre) + 1 * D, one(), B);
+    fwd(c->obj, w(x.oem), flat(n.od), w(x.pre) + 2 * D, one(), B);
+    fwd(c->pose, io.pose, flat(n.F), w(x.cat), flat(2 * D), n.BT);
+    fwd(c->traj, w(x.trm), flat(n.qd), w(x.cat) + D, flat(2 * D), n.BT);
+    fwd(c->m0, w(x.cat), flat(2 * D), w(x.z), flat(D), n.BT, silu(w(x.zpre)));
+    fwd(c->m2, w(x.z), flat(D), w(x.pre) + ENC_P * D, frames(), n.BT);
+    launch(assemble_kernel, blocks(n.R * D, 256), 256, 0, w(x.pre), c->pe->p, xof(0), nullptr, nullptr, B, S, drop);
+  }
+  void forward_layer(int l) {
+    const LayerWs& x = c->lw[l];
+    const LayerP& p = c->lp[l];
+    const LayerView v = layer_view(l);
+    const long o = v.o64, of = v.off;
+    fwd(p.inproj, xof(l), flat(D), w(x.qkv), flat(3 * D), n.R);
+    launch(attn_fwd_kernel, dim3((v.nq + 63) / 64, EG_H, B), 64, att_lds(),
+           AttnArgs{w(x.qkv), w(x.att), w(x.stat), nullptr, nullptr, nullptr, S, v.q0, v.site, drop});
+    fwd(p.out, w(x.att) + o, v.r64, w(x.x1pre) + o, v.r64, v.M, drop_res(xof(l) + o, v.site + 1, v.q0));
+    ln_fwd(v, w(x.x1pre) + o, w(x.x1) + o, p.n1);
+    fwd(p.l1, w(x.x1) + o, v.r64, w(x.gel) + of, v.rff, v.M, gelu_drop(w(x.hpre) + of, v.site + 2, v.q0));
+    fwd(p.l2, w(x.gel) + of, v.rff, w(x.x2pre) + o, v.r64, v.M, drop_res(w(x.x1) + o, v.site + 3, v.q0));
+    ln_fwd(v, w(x.x2pre) + o, xof(l + 1) + o, p.n2);
+  }
+  void forward_head_and_loss() {
+    const HeadWs& h = c->head;
+    fwd(c->p0, cls_rows(), one(), w(h.h1), flat(D), B, silu(w(h.h1pre)));
+    fwd(c->p2, w(h.h1), flat(D), w(h.h2), flat(D), B, silu(w(h.h2pre)));
+    fwd(c->p4, w(h.h2), flat(D), io.act, flat(n.F), B);
+    launch(ce_kernel, 1, 256, 0, io.act, io.labels, B, n.F, w(c->g.lb), w(c->g.dact), io.loss);
+  }
+  void backward_head() {
+    const HeadWs& h = c->head;
+    const GradWs& g = c->g;
+    wgrad(c->p4, w(g.dact), flat(n.F), w(h.h2), flat(D), B);
+    dgrad(c->p4, w(g.dact), flat(n.F), w(g.dh2), flat(D), B, bwd_silu(w(h.h2pre)));
+    wgrad(c->p2, w(g.dh2), flat(D), w(h.h1), flat(D), B);
+    dgrad(c->p2, w(g.dh2), flat(D), w(g.dh1), flat(D), B, bwd_silu(w(h.h1pre)));
+    wgrad(c->p0, w(g.dh1), flat(D), cls_rows(), one(), B);
+    dgrad(c->p0, w(g.dh1), flat(D), w(g.dx) + (long)(S - 1) * D, one(), B);
+  }
+  void backward_layer(int l) {
+    const LayerWs& x = c->lw[l];
+    const LayerP& p = c->lp[l];
+    const GradWs& g = c->g;
+    const LayerView v = layer_view(l);
+    const long o = v.o64, of = v.off;
+    // LayerNorm 2, the feed-forward block
+    ln_bwd(v, g.dx, x.x2pre, p.n2, v.site + 3);
+    wgrad(p.l2, w(g.dym) + o, v.r64, w(x.gel) + of, v.rff, v.M);
+    dgrad(p.l2, w(g.dym) + o, v.r64, w(g.dh) + of, v.rff, v.M, bwd_gelu_drop(w(x.hpre) + of, v.site + 2, v.q0));
+    wgrad(p.l1, w(g.dh) + of, v.rff, w(x.x1) + o, v.r64, v.M);
+    dgrad(p.l1, w(g.dh) + of, v.rff, w(g.dx1) + o, v.r64, v.M, bwd_res(w(g.dz) + o));
+    // LayerNorm 1, out-projection, attention, in-projection
+    ln_bwd(v, g.dx1, x.x1pre, p.n1, v.site + 1);
+    wgrad(p.out, w(g.dym) + o, v.r64, w(x.att) + o, v.r64, v.M);
+    dgrad(p.out, w(g.dym) + o, v.r64, w(g.datt) + o, v.r64, v.M);
+    const AttnArgs a{w(x.qkv), nullptr, w(x.stat), w(g.datt), w(g.dqkv), w(g.delta), S, v.q0, v.site, drop};
+    launch(attn_bwd_q_kernel, dim3((S + 63) / 64, EG_H, B), 64, att_lds(), a);
+    launch(attn_bwd_kv_kernel, dim3((S + 63) / 64, EG_H, B), 64, att_lds(), a);
+    wgrad(p.inproj, w(g.dqkv), flat(3 * D), xof(l), flat(D), n.R);
+    dgrad(p.inproj, w(g.dqkv), flat(3 * D), w(g.dx), rows(S, D), n.R, bwd_res_q0(w(g.dz), v.q0));
+  }
+  void backward_input() {
+    const InputWs& x = c->in;
+    const GradWs& g = c->g;
+    launch(assemble_kernel, blocks(n.R * D, 256), 256, 0, w(x.pre), c->pe->p, nullptr, w(g.dx), w(g.dpre), B, S, drop);
+    wgrad(c->shape, w(g.dpre) + 1 * D, one(), w(x.shm), flat(n.sd), B);
+    wgrad(c->obj, w(g.dpre) + 2 * D, one(), w(x.oem), flat(n.od), B);
+    const float* dfr = w(g.dpre) + ENC_P * D;
+    wgrad(c->m2, dfr, frames(), w(x.z), flat(D), n.BT);
+    dgrad(c->m2, dfr, frames(), w(g.dzin), flat(D), n.BT, bwd_silu(w(x.zpre)));
+    wgrad(c->m0, w(g.dzin), flat(D), w(x.cat), flat(2 * D), n.BT);
+    dgrad(c->m0, w(g.dzin), flat(D), w(g.dcat), flat(2 * D), n.BT);
+    wgrad(c->pose, w(g.dcat), flat(2 * D), io.pose, flat(n.F), n.BT);
+    wgrad(c->traj, w(g.dcat) + D, flat(2 * D), w(x.trm), flat(n.qd), n.BT);
   }
 };
 
@@ -185,85 +405,16 @@ int tamf_enctrain_create(const tamf_arch* arch, int32_t max_batch, int32_t max_f
   c->maxB = max_batch;
   c->maxT = max_frames;
   c->device = device;
-  const int d = ENC_D, F = arch->input_dim, ff = arch->ff_size, L = arch->num_layers, sd = arch->hand_shape_dim, od = arch->obj_embed_dim,
-            qd = arch->obj_input_dim;
-  declare(c, "hand_side_process.rh_embed", {d}, false);
-  declare(c, "hand_side_process.lh_embed", {d}, false);
-  declare_linear(c, "hand_shape_process.shape_embed", d, sd);
-  declare_linear(c, "obj_embed_process.embedding", d, od);
-  declare(c, "classification_token", {1, 1, d}, false);
-  declare_linear(c, "input_process.poseEmbedding", d, F);
-  declare_linear(c, "obj_input_process.poseEmbedding", d, qd);
-  declare_linear(c, "input_merge.0", d, 2 * d);
-  declare_linear(c, "input_merge.2", d, d);
-  declare(c, "sequence_pos_encoder.pe", {5000, 1, d}, false);
-  for (int l = 0; l < L; ++l) {
-    const std::string p = "seqTransEncoder.layers." + std::to_string(l) + ".";
-    declare(c, p + "self_attn.in_proj_weight", {3 * d, d});
-    declare(c, p + "self_attn.in_proj_bias", {3 * d});
-    declare_linear(c, p + "self_attn.out_proj", d, d);
-    declare_linear(c, p + "linear1", ff, d);
-    declare_linear(c, p + "linear2", d, ff);
-    declare(c, p + "norm1.weight", {d});
-    declare(c, p + "norm1.bias", {d});
-    declare(c, p + "norm2.weight", {d});
-    declare(c, p + "norm2.bias", {d});
-  }
-  declare_linear(c, "output_process.poseFinal.0", d, d);
-  declare_linear(c, "output_process.poseFinal.2", d, d);
-  declare_linear(c, "output_process.poseFinal.4", F, d);
-
-  const long Bm = max_batch, R = Bm * (max_frames + ENC_P + 1), BT = Bm * max_frames;
+  declare_model(c);
+  const Dims n = dims(*arch, max_batch, max_frames);
   Carver cv;
-  c->shm = cv.take(Bm * sd);
-  c->oem = cv.take(Bm * od);
-  c->trm = cv.take(BT * qd);
-  c->cat = cv.take(BT * 2 * d);
-  c->zpre = cv.take(BT * d);
-  c->z = cv.take(BT * d);
-  c->pre = cv.take(R * d);
-  c->lw.resize(L);
-  for (int l = 0; l < L; ++l) {
-    LayerWs& x = c->lw[l];
-    x.x = cv.take(R * d);
-    x.qkv = cv.take(R * 3 * d);
-    x.stat = cv.take(R * EG_H * 2);
-    x.att = cv.take(R * d);
-    x.x1pre = cv.take(R * d);
-    x.x1 = cv.take(R * d);
-    x.x2pre = cv.take(R * d);
-    x.hpre = cv.take(R * ff);
-    x.gel = cv.take(R * ff);
-  }
-  c->xlast = cv.take(R * d);
-  c->h1pre = cv.take(Bm * d);
-  c->h1 = cv.take(Bm * d);
-  c->h2pre = cv.take(Bm * d);
-  c->h2 = cv.take(Bm * d);
-  c->dx = cv.take(R * d);
-  c->dz = cv.take(R * d);
-  c->dym = cv.take(R * d);
-  c->tt = cv.take(R * d);
-  c->dx1 = cv.take(R * d);
-  c->datt = cv.take(R * d);
-  c->dqkv = cv.take(R * 3 * d);
-  c->dh = cv.take(R * ff);
-  c->delta = cv.take(R * EG_H);
-  c->dpre = cv.take(R * d);
-  c->dzin = cv.take(BT * d);
-  c->dcat = cv.take(BT * 2 * d);
-  c->dact = cv.take(Bm * F);
-  c->dh1 = cv.take(Bm * d);
-  c->dh2 = cv.take(Bm * d);
-  c->lb = cv.take(Bm);
-  long nk = 0;  // the largest N * (K + 1) of a linear map
-  for (long v : {(long)d * (sd + 1), (long)d * (od + 1), (long)d * (F + 1), (long)d * (qd + 1), (long)d * (2 * d + 1), (long)3 * d * (d + 1), (long)ff * (d + 1),
-                 (long)d * (ff + 1), (long)F * (d + 1)})
-    nk = std::max(nk, v);
-  c->slab = cv.take(nk * MAX_SPLIT);
+  c->in = carve_input(cv, n);
+  for (int l = 0; l < arch->num_layers; ++l) c->lw.push_back(carve_layer(cv, n));
+  c->head = carve_head(cv, n);
+  c->g = carve_grads(cv, n, c->slab_nk);
   e = hipMalloc((void**)&c->ws, cv.total * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&c->cnt, Bm * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc((void**)&c->clip, Bm * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&c->cnt, n.B * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&c->clip, n.B * sizeof(long long));
   if (e != hipSuccess) {
     const std::string msg = std::string("hipMalloc of the workspace (") + std::to_string(cv.total * sizeof(float)) + " bytes): " + hipGetErrorString(e);
     tamf_enctrain_destroy(c);
@@ -283,16 +434,12 @@ void tamf_enctrain_destroy(tamf_enctrain_ctx* c) {
 
 int tamf_enctrain_bind(tamf_enctrain_ctx* c, const char* name, const float* param_dev, float* grad_dev, const int64_t* shape, int32_t ndim) {
   if (!c || !name || !param_dev || ndim < 0 || (ndim > 0 && !shape)) return fail(TAMF_ERR_INVALID, "null argument");
-  auto it = c->t.find(name);
-  if (it == c->t.end()) return fail(TAMF_ERR_INVALID, std::string("unknown key '") + name + "'");
-  Bound& b = it->second;
-  if ((size_t)ndim != b.shape.size() || !std::equal(b.shape.begin(), b.shape.end(), shape))
-    return fail(TAMF_ERR_INVALID, std::string(name) + ": expected shape " + shape_str(b.shape.data(), (int)b.shape.size()) + ", got " + shape_str(shape, ndim));
-  if (b.trainable && !grad_dev) return fail(TAMF_ERR_INVALID, std::string(name) + ": a trainable tensor needs a gradient buffer");
-  if (!b.trainable && grad_dev) return fail(TAMF_ERR_INVALID, std::string(name) + ": a buffer takes no gradient");
-  b.p = param_dev;
-  b.g = grad_dev;
-  c->resolved = false;
+  Bound* b = find_declared(c->t, name, shape, ndim);
+  if (!b) return TAMF_ERR_INVALID;
+  if (b->trainable && !grad_dev) return fail(TAMF_ERR_INVALID, std::string(name) + ": a trainable tensor needs a gradient buffer");
+  if (!b->trainable && grad_dev) return fail(TAMF_ERR_INVALID, std::string(name) + ": a buffer takes no gradient");
+  b->p = param_dev;
+  b->g = grad_dev;
   return 0;
 }
 
@@ -310,243 +457,30 @@ int tamf_enctrain_step(tamf_enctrain_ctx* c, int32_t B, int32_t T, int32_t nobj,
     for (int b = 0; b < B; ++b)
       if (obj_num_host[b] < 1 || obj_num_host[b] > nobj)
         return fail(TAMF_ERR_INVALID, "obj_num[" + std::to_string(b) + "] = " + std::to_string(obj_num_host[b]) + " outside [1, nobj = " + std::to_string(nobj) + "]");
-  if (!c->resolved) {  // (the first step after a bind: every tensor has to be there, then the pointers are looked up once)
-    for (const std::string& k : c->order)
-      if (!c->t[k].p) return fail(TAMF_ERR_MISSING, "missing binding '" + k + "'");
-    resolve(c);
-  }
+  for (const auto* kv : c->order)  // every tensor has to be there before anything is launched
+    if (!kv->second.p) return fail(TAMF_ERR_MISSING, "missing binding '" + kv->first + "'");
   hipError_t e = hipSetDevice(c->device);
   if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  hipStream_t st = (hipStream_t)stream;
+  if (obj_num_host) e = hipMemcpyAsync(c->cnt, obj_num_host, B * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && clip_id_host) e = hipMemcpyAsync(c->clip, clip_id_host, B * sizeof(long long), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
 
   Step s;
   s.c = c;
-  s.st = (hipStream_t)stream;
-  s.B = B;
-  s.T = T;
-  s.S = T + ENC_P + 1;
-  const int S = s.S, d = ENC_D, F = c->arch.input_dim, ff = c->arch.ff_size, L = c->arch.num_layers, sd = c->arch.hand_shape_dim,
-            od = c->arch.obj_embed_dim, qd = c->arch.obj_input_dim, BT = B * T, BS = B * S;
-  hipStream_t st = s.st;
-  if (obj_num_host) {
-    e = hipMemcpyAsync(c->cnt, obj_num_host, B * sizeof(int), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
-  }
-  if (clip_id_host) {
-    e = hipMemcpyAsync(c->clip, clip_id_host, B * sizeof(long long), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
-  }
-  s.d.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  s.d.k1 = (uint32_t)(seed >> 32);
-  s.d.step = step;
-  s.d.thr = (uint32_t)std::min(4294967295.0, std::floor((double)dropout_p * 4294967296.0));
-  s.d.scale = 1.0f / (1.0f - dropout_p);
-  s.d.clip = clip_id_host ? c->clip : nullptr;
-  const Drop& dr = s.d;
-  auto w = [&](long off) { return c->ws + off; };
-  const size_t att_lds = (size_t)S * ENC_HD * 2 * sizeof(float);
-
-  // ---------------- forward ----------------
-  {
-    PrepArgs a{shape_dev, obj_emb_dev, obj_traj_dev, hand_side_dev, obj_num_host ? c->cnt : nullptr, c->rh, c->lh, c->cls, w(c->shm), w(c->oem), w(c->trm), w(c->pre), B, T, nobj, sd, od, qd};
-    const long n = (long)B * sd + (long)B * od + (long)BT * qd + (long)B * 2 * d;
-    prep_kernel<<<blocks(n, 256), 256, 0, st>>>(a);
-    s.check();
-  }
-  const RowMap one = RowMap{1, (long)S * d, d};  // one row of every clip inside [B][S][64]
-  auto base_lin = [&](const float* A, RowMap am, const Lin& lin, float* C, RowMap cm, int M, int N, int K) {
-    LinArgs a{};
-    a.A = A;
-    a.am = am;
-    a.W = lin.w;
-    a.swn = K;
-    a.swk = 1;
-    a.bias = lin.b;
-    a.C = C;
-    a.cm = cm;
-    a.rm = cm;
-    a.M = M;
-    a.N = N;
-    a.K = K;
-    a.mode = EG_LIN;
-    return a;
-  };
-  // the data gradient of the same map: dA (M, K) = dY (M, N) . W
-  auto base_dgrad = [&](const float* dY, RowMap ym, const Lin& lin, int N, int K, float* C, RowMap cm, int M) {
-    LinArgs a{};
-    a.A = dY;
-    a.am = ym;
-    a.W = lin.w;
-    a.swn = 1;
-    a.swk = K;
-    a.C = C;
-    a.cm = cm;
-    a.rm = cm;
-    a.M = M;
-    a.N = K;
-    a.K = N;
-    a.mode = EG_LIN;
-    return a;
-  };
-  s.lin(base_lin(w(c->shm), flat(sd), c->shape, w(c->pre) + 1 * d, one, B, d, sd));
-  s.lin(base_lin(w(c->oem), flat(od), c->obj, w(c->pre) + 2 * d, one, B, d, od));
-  s.lin(base_lin(pose_dev, flat(F), c->pose, w(c->cat), flat(2 * d), BT, d, F));
-  s.lin(base_lin(w(c->trm), flat(qd), c->traj, w(c->cat) + d, flat(2 * d), BT, d, qd));
-  {
-    LinArgs a = base_lin(w(c->cat), flat(2 * d), c->m0, w(c->z), flat(d), BT, d, 2 * d);
-    a.mode = EG_SILU;
-    a.C2 = w(c->zpre);
-    s.lin(a);
-  }
-  const RowMap frames = RowMap{T, (long)S * d, d};
-  s.lin(base_lin(w(c->z), flat(d), c->m2, w(c->pre) + ENC_P * d, frames, BT, d, d));
-  const float* pe = c->pe;
-  auto xof = [&](int l) { return w(l < L ? c->lw[l].x : c->xlast); };
-  assemble_kernel<<<blocks((long)BS * d, 256), 256, 0, st>>>(w(c->pre), pe, xof(0), nullptr, nullptr, B, S, dr);
-  s.check();
-
-  for (int l = 0; l < L; ++l) {
-    const LayerWs& x = c->lw[l];
-    const LayerP& lp = c->lp[l];
-    const int q0 = l == L - 1 ? S - 1 : 0, nq = S - q0, M = B * nq, site = 1 + 4 * l;
-    const RowMap r64 = s.rows(nq, d), rff = s.rows(nq, ff);
-    const long o64 = (long)q0 * d, off = (long)q0 * ff;
-    s.lin(base_lin(xof(l), flat(d), lp.inproj, w(x.qkv), flat(3 * d), BS, 3 * d, d));
-    {
-      AttnArgs a{w(x.qkv), w(x.att), w(x.stat), nullptr, nullptr, nullptr, S, q0, site, dr};
-      attn_fwd_kernel<<<dim3((nq + 63) / 64, EG_H, B), 64, att_lds, st>>>(a);
-      s.check();
-    }
-    {
-      LinArgs a = base_lin(w(x.att) + o64, r64, lp.out, w(x.x1pre) + o64, r64, M, d, d);
-      a.mode = EG_DROP_RES;
-      a.R = xof(l) + o64;
-      a.site = site + 1;
-      a.q0 = q0;
-      s.lin(a);
-    }
-    ln_fwd_kernel<<<blocks(M, 4), 256, 0, st>>>(w(x.x1pre) + o64, r64, w(x.x1) + o64, r64, lp.n1.w, lp.n1.b, M);
-    s.check();
-    {
-      LinArgs a = base_lin(w(x.x1) + o64, r64, lp.l1, w(x.gel) + off, rff, M, ff, d);
-      a.mode = EG_GELU_DROP;
-      a.C2 = w(x.hpre) + off;
-      a.site = site + 2;
-      a.q0 = q0;
-      s.lin(a);
-    }
-    {
-      LinArgs a = base_lin(w(x.gel) + off, rff, lp.l2, w(x.x2pre) + o64, r64, M, d, ff);
-      a.mode = EG_DROP_RES;
-      a.R = w(x.x1) + o64;
-      a.site = site + 3;
-      a.q0 = q0;
-      s.lin(a);
-    }
-    ln_fwd_kernel<<<blocks(M, 4), 256, 0, st>>>(w(x.x2pre) + o64, r64, xof(l + 1) + o64, r64, lp.n2.w, lp.n2.b, M);
-    s.check();
-  }
-  const float* enc = xof(L) + (long)(S - 1) * d;  // the classification rows, at `one`
-  {
-    LinArgs a = base_lin(enc, one, c->p0, w(c->h1), flat(d), B, d, d);
-    a.mode = EG_SILU;
-    a.C2 = w(c->h1pre);
-    s.lin(a);
-    a = base_lin(w(c->h1), flat(d), c->p2, w(c->h2), flat(d), B, d, d);
-    a.mode = EG_SILU;
-    a.C2 = w(c->h2pre);
-    s.lin(a);
-    s.lin(base_lin(w(c->h2), flat(d), c->p4, activation_out_dev, flat(F), B, F, d));
-  }
-  ce_kernel<<<1, 256, 0, st>>>(activation_out_dev, (const long long*)labels_dev, B, F, w(c->lb), w(c->dact), loss_out_dev);
-  s.check();
-
-  // ---------------- backward ----------------
-  s.wgrad(w(c->dact), flat(F), w(c->h2), flat(d), B, F, d, c->p4);
-  {
-    LinArgs a = base_dgrad(w(c->dact), flat(F), c->p4, F, d, w(c->dh2), flat(d), B);
-    a.mode = EG_BWD_SILU;
-    a.R = w(c->h2pre);
-    s.lin(a);
-    s.wgrad(w(c->dh2), flat(d), w(c->h1), flat(d), B, d, d, c->p2);
-    a = base_dgrad(w(c->dh2), flat(d), c->p2, d, d, w(c->dh1), flat(d), B);
-    a.mode = EG_BWD_SILU;
-    a.R = w(c->h1pre);
-    s.lin(a);
-    s.wgrad(w(c->dh1), flat(d), enc, one, B, d, d, c->p0);
-    s.lin(base_dgrad(w(c->dh1), flat(d), c->p0, d, d, w(c->dx) + (long)(S - 1) * d, one, B));
-  }
-  for (int l = L - 1; l >= 0; --l) {
-    const LayerWs& x = c->lw[l];
-    const LayerP& lp = c->lp[l];
-    const int q0 = l == L - 1 ? S - 1 : 0, nq = S - q0, M = B * nq, site = 1 + 4 * l;
-    const RowMap r64 = s.rows(nq, d), rff = s.rows(nq, ff);
-    const long o64 = (long)q0 * d, off = (long)q0 * ff;
-    // LayerNorm 2, linear2, GELU, linear1
-    ln_bwd_kernel<<<blocks(M, 4), 256, 0, st>>>(w(c->dx) + o64, w(x.x2pre) + o64, r64, lp.n2.w, w(c->dz) + o64, w(c->dym) + o64,
-                                                w(c->tt) + o64, M, q0, site + 3, dr);
-    s.check();
-    s.colsum(w(c->tt) + o64, r64, M, lp.n2.gw);
-    s.colsum(w(c->dx) + o64, r64, M, lp.n2.gb);
-    s.wgrad(w(c->dym) + o64, r64, w(x.gel) + off, rff, M, d, ff, lp.l2);
-    {
-      LinArgs a = base_dgrad(w(c->dym) + o64, r64, lp.l2, d, ff, w(c->dh) + off, rff, M);
-      a.mode = EG_BWD_GELU_DROP;
-      a.R = w(x.hpre) + off;
-      a.site = site + 2;
-      a.q0 = q0;
-      s.lin(a);
-    }
-    s.wgrad(w(c->dh) + off, rff, w(x.x1) + o64, r64, M, ff, d, lp.l1);
-    {
-      LinArgs a = base_dgrad(w(c->dh) + off, rff, lp.l1, ff, d, w(c->dx1) + o64, r64, M);
-      a.mode = EG_BWD_RES;
-      a.R = w(c->dz) + o64;
-      s.lin(a);
-    }
-    // LayerNorm 1, out-projection, attention, in-projection
-    ln_bwd_kernel<<<blocks(M, 4), 256, 0, st>>>(w(c->dx1) + o64, w(x.x1pre) + o64, r64, lp.n1.w, w(c->dz) + o64, w(c->dym) + o64,
-                                                w(c->tt) + o64, M, q0, site + 1, dr);
-    s.check();
-    s.colsum(w(c->tt) + o64, r64, M, lp.n1.gw);
-    s.colsum(w(c->dx1) + o64, r64, M, lp.n1.gb);
-    s.wgrad(w(c->dym) + o64, r64, w(x.att) + o64, r64, M, d, d, lp.out);
-    s.lin(base_dgrad(w(c->dym) + o64, r64, lp.out, d, d, w(c->datt) + o64, r64, M));
-    {
-      AttnArgs a{w(x.qkv), nullptr, w(x.stat), w(c->datt), w(c->dqkv), w(c->delta), S, q0, site, dr};
-      attn_bwd_q_kernel<<<dim3((S + 63) / 64, EG_H, B), 64, att_lds, st>>>(a);
-      s.check();
-      attn_bwd_kv_kernel<<<dim3((S + 63) / 64, EG_H, B), 64, att_lds, st>>>(a);
-      s.check();
-    }
-    s.wgrad(w(c->dqkv), flat(3 * d), xof(l), flat(d), BS, 3 * d, d, lp.inproj);
-    {
-      LinArgs a = base_dgrad(w(c->dqkv), flat(3 * d), lp.inproj, 3 * d, d, w(c->dx), s.rows(S, d), BS);
-      a.mode = EG_BWD_RES_Q0;
-      a.R = w(c->dz);
-      a.rq0 = q0;
-      s.lin(a);
-    }
-  }
-  // input stage
-  assemble_kernel<<<blocks((long)BS * d, 256), 256, 0, st>>>(w(c->pre), pe, nullptr, w(c->dx), w(c->dpre), B, S, dr);
-  s.check();
-  s.wgrad(w(c->dpre) + 1 * d, one, w(c->shm), flat(sd), B, d, sd, c->shape);
-  s.wgrad(w(c->dpre) + 2 * d, one, w(c->oem), flat(od), B, d, od, c->obj);
-  const float* dfr = w(c->dpre) + ENC_P * d;
-  s.wgrad(dfr, frames, w(c->z), flat(d), BT, d, d, c->m2);
-  {
-    LinArgs a = base_dgrad(dfr, frames, c->m2, d, d, w(c->dzin), flat(d), BT);
-    a.mode = EG_BWD_SILU;
-    a.R = w(c->zpre);
-    s.lin(a);
-  }
-  s.wgrad(w(c->dzin), flat(d), w(c->cat), flat(2 * d), BT, d, 2 * d, c->m0);
-  s.lin(base_dgrad(w(c->dzin), flat(d), c->m0, d, 2 * d, w(c->dcat), flat(2 * d), BT));
-  s.wgrad(w(c->dcat), flat(2 * d), pose_dev, flat(F), BT, d, F, c->pose);
-  s.wgrad(w(c->dcat) + d, flat(2 * d), w(c->trm), flat(qd), BT, d, qd, c->traj);
-
-  if (s.err != hipSuccess) return fail(TAMF_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(s.err));
-  return 0;
+  s.st = st;
+  s.n = dims(c->arch, B, T);
+  s.B = B, s.T = T, s.S = T + ENC_P + 1;
+  s.io = Batch{pose_dev, shape_dev, obj_emb_dev, obj_traj_dev, hand_side_dev, obj_num_host ? c->cnt : nullptr, (const long long*)labels_dev, loss_out_dev, activation_out_dev, nobj};
+  s.drop = make_drop(seed, step, dropout_p, clip_id_host ? c->clip : nullptr);
+  const int L = c->arch.num_layers;
+  s.forward_input();
+  for (int l = 0; l < L; ++l) s.forward_layer(l);
+  s.forward_head_and_loss();
+  s.backward_head();
+  for (int l = L - 1; l >= 0; --l) s.backward_layer(l);
+  s.backward_input();
+  return s.status();
 }
 
 int tamf_enctrain_dropout_mask(uint64_t seed, uint32_t step, int64_t clip_id, int32_t site, int32_t rows, int32_t cols, float p,
@@ -555,18 +489,11 @@ int tamf_enctrain_dropout_mask(uint64_t seed, uint32_t step, int64_t clip_id, in
   if (rows < 1 || cols < 1 || (long)rows * cols > 0xFFFFFFFFL) return fail(TAMF_ERR_INVALID, "rows * cols must be in [1, 2^32)");
   if (site < 0) return fail(TAMF_ERR_INVALID, "site must be >= 0");
   if (!(p >= 0.f && p < 1.f)) return fail(TAMF_ERR_INVALID, "p must be in [0, 1)");
-  Drop d;
-  d.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  d.k1 = (uint32_t)(seed >> 32);
-  d.step = step;
-  d.thr = (uint32_t)std::min(4294967295.0, std::floor((double)p * 4294967296.0));
-  d.scale = 1.0f / (1.0f - p);
-  d.clip = nullptr;
+  Step s;
+  s.st = (hipStream_t)stream;
   const long n = (long)rows * cols;
-  dropout_mask_kernel<<<blocks(n, 256), 256, 0, (hipStream_t)stream>>>(d, site, (unsigned long long)clip_id, n, out_dev);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return 0;
+  s.launch(dropout_mask_kernel, blocks(n, 256), 256, 0, make_drop(seed, step, p, nullptr), site, (unsigned long long)clip_id, n, out_dev);
+  return s.status();
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
-// Host side of the native model libraries that take a state dict tensor by tensor (libtamf_pointenc.so, libtamf_textenc.so): the
-// last-error string, the table of declared tensors with its checks, the packer and the upload of the device weight buffer, and the
-// small helpers of an encode call.  Host only; each library compiles its own copy (its own error string) and calls the steps in its
+// Host side of the native model libraries that take a state dict tensor by tensor (libtamf_pointenc.so, libtamf_textenc.so, and
+// libtamf_enctrain.so, which binds the tensors where they live): the last-error string, the table of declared tensors with its checks,
+// the packer and the upload of the device weight buffer, and the small helpers of an encode call.  Host only; each library compiles its own copy (its own error string) and calls the steps in its
 // own order.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -40,6 +40,18 @@ std::string shape_str(const int64_t* s, int n) {
   return r + ")";
 }
 
+// the entry declared under `key` in a table of tensors (anything with a `shape`), or null with the error set: an unknown key, or a
+// shape other than the declared one
+template <class T>
+T* find_declared(std::map<std::string, T>& t, const char* key, const int64_t* shape, int32_t ndim) {
+  auto it = t.find(key);
+  if (it == t.end()) return fail(TAMF_ERR_INVALID, std::string("unknown key '") + key + "'"), nullptr;
+  T& x = it->second;
+  if ((size_t)ndim != x.shape.size() || !std::equal(x.shape.begin(), x.shape.end(), shape))
+    return fail(TAMF_ERR_INVALID, std::string(key) + ": expected shape " + shape_str(x.shape.data(), (int)x.shape.size()) + ", got " + shape_str(shape, ndim)), nullptr;
+  return &x;
+}
+
 struct WeightTable {
   std::vector<std::string> order;  // the keys in state-dict order
   std::map<std::string, Tensor> t;
@@ -56,13 +68,10 @@ struct WeightTable {
   int load(const char* key, const float* host, int32_t ndim, const int64_t* shape) {
     if (!key || !host || (ndim > 0 && !shape) || ndim < 0) return fail(TAMF_ERR_INVALID, "null argument");
     if (closed) return fail(TAMF_ERR_STATE, "the model is finalised");
-    auto it = t.find(key);
-    if (it == t.end()) return fail(TAMF_ERR_INVALID, std::string("unknown key '") + key + "'");
-    Tensor& x = it->second;
-    if ((size_t)ndim != x.shape.size() || !std::equal(x.shape.begin(), x.shape.end(), shape))
-      return fail(TAMF_ERR_INVALID, std::string(key) + ": expected shape " + shape_str(x.shape.data(), (int)x.shape.size()) + ", got " + shape_str(shape, ndim));
-    x.data.assign(host, host + x.numel());
-    x.loaded = true;
+    Tensor* x = find_declared(t, key, shape, ndim);
+    if (!x) return TAMF_ERR_INVALID;
+    x->data.assign(host, host + x->numel());
+    x->loaded = true;
     return 0;
   }
 

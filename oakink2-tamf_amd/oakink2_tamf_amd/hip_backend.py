@@ -158,6 +158,33 @@ def _dev_f32(t: torch.Tensor, device: torch.device) -> torch.Tensor:
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+def obj_num_vector(obj_num: Optional[Sequence[int]], B: int) -> Optional[np.ndarray]:
+    """per-clip object counts as the contiguous int32 vector the C entry points read; None stays None"""
+    if obj_num is None:
+        return None
+    num_np = np.ascontiguousarray(torch.as_tensor(obj_num).cpu().numpy() if isinstance(obj_num, torch.Tensor) else obj_num, dtype=np.int32)
+    if num_np.shape != (B,):
+        raise ValueError(f"obj_num must hold one count per clip: shape {num_np.shape} for B = {B}")
+    return num_np
+
+
+def encoder_batch(batch: Mapping, obj_num: Optional[Sequence[int]], device: torch.device, input_dim: int, n_labels: Optional[int] = None):
+    """What both SegmentEncoder entry points (TamfContext.encode, SegmentEncoderTrainStep.loss_and_grads) make of a batch -
+    "pose_repr" (B, T, input_dim), "shape" (B, T, 10), "hand_side" B x "rh"/"lh", "obj_embedding" (B, nobj, od), "obj_traj"
+    (B, nobj, T, 9) - and obj_num: the four float32 device tensors, (B, T, F, nobj), the int32 obj_num vector or None, and the uint8
+    hand-side tensor on the device.  ValueError when the shapes do not agree; n_labels (the training step's label count) joins the check."""
+    side = [hand_side_code(hs) for hs in batch["hand_side"]]
+    pr, sh = _dev_f32(batch["pose_repr"], device), _dev_f32(batch["shape"], device)
+    oe, ot = _dev_f32(batch["obj_embedding"], device), _dev_f32(batch["obj_traj"], device)
+    B, T, F = pr.shape
+    nobj = ot.shape[1]
+    if F != input_dim or tuple(sh.shape[:2]) != (B, T) or tuple(oe.shape[:2]) != (B, nobj) or tuple(ot.shape[:3]) != (B, nobj, T) \
+            or len(side) != B or n_labels not in (None, B):
+        raise ValueError(f"inconsistent encoder inputs: pose_repr {tuple(pr.shape)}, shape {tuple(sh.shape)}, obj_embedding "
+                         f"{tuple(oe.shape)}, obj_traj {tuple(ot.shape)}, {len(side)} hand sides" + ("" if n_labels is None else f", {n_labels} labels"))
+    return (pr, sh, oe, ot), (B, T, F, nobj), obj_num_vector(obj_num, B), torch.tensor(side, dtype=torch.uint8, device=device)
+
+
 def require_gpu(device=None) -> torch.device:
     if not torch.cuda.is_available():
         raise TamfError("no MI355X/HIP device visible: the MF-MDM HIP path has no CPU fallback")
@@ -276,11 +303,7 @@ class TamfContext:
         assert sh.shape[0] == B and sh.shape[1] == T and oe.shape[0] == B and oe.shape[1] == nobj
         side_np = np.asarray(side, dtype=np.uint8)
         assert side_np.shape[0] == B
-        num_np = None
-        if obj_num is not None:
-            num_np = np.ascontiguousarray(torch.as_tensor(obj_num).cpu().numpy() if isinstance(obj_num, torch.Tensor) else obj_num, dtype=np.int32)
-            if num_np.shape != (B,):
-                raise ValueError(f"obj_num must hold one count per clip: shape {num_np.shape} for B = {B}")
+        num_np = obj_num_vector(obj_num, B)
         if num_np is None and not hasattr(self._L, "tamf_set_cond_ragged"):  # (an older A/B build loaded through _lib.load_from)
             with torch.cuda.device(dev):
                 self._check(self._L.tamf_set_cond(self._h, B, T, nobj, c_void_p(te.data_ptr() if te is not None else 0), side_np.ctypes.data_as(c_void_p),
@@ -327,21 +350,9 @@ class TamfContext:
         obj_num: per-clip object counts (the reference FID script's batches of one clip); None: means over all nobj rows."""
         if self.kind != "E":
             raise TamfError(f"encode needs a SegmentEncoder context (kind 'E'), this one is kind {self.kind!r}")
-        side = [hand_side_code(hs) for hs in hand_side]
         dev = self.device
-        pr, sh, oe, ot = _dev_f32(pose_repr, dev), _dev_f32(shape, dev), _dev_f32(obj_embedding, dev), _dev_f32(obj_traj, dev)
-        B, T, F = pr.shape
-        nobj = ot.shape[1]
-        if F != self.input_dim or tuple(sh.shape[:2]) != (B, T) or tuple(oe.shape[:2]) != (B, nobj) or tuple(ot.shape[:3]) != (B, nobj, T) \
-                or len(side) != B:
-            raise ValueError(f"inconsistent encoder inputs: pose_repr {tuple(pr.shape)}, shape {tuple(sh.shape)}, obj_embedding "
-                             f"{tuple(oe.shape)}, obj_traj {tuple(ot.shape)}, {len(side)} hand sides")
-        num_np = None
-        if obj_num is not None:
-            num_np = np.ascontiguousarray(torch.as_tensor(obj_num).cpu().numpy() if isinstance(obj_num, torch.Tensor) else obj_num, dtype=np.int32)
-            if num_np.shape != (B,):
-                raise ValueError(f"obj_num must hold one count per clip: shape {num_np.shape} for B = {B}")
-        side_d = torch.tensor(side, dtype=torch.uint8, device=dev)
+        batch = dict(pose_repr=pose_repr, shape=shape, hand_side=hand_side, obj_embedding=obj_embedding, obj_traj=obj_traj)
+        (pr, sh, oe, ot), (B, T, F, nobj), num_np, side_d = encoder_batch(batch, obj_num, dev, self.input_dim)
         enc = torch.empty(B, self.latent_dim, dtype=torch.float32, device=dev)
         act = torch.empty(B, F, dtype=torch.float32, device=dev) if with_activation else None
         with torch.cuda.device(dev):

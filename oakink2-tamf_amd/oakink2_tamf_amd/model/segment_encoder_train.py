@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..hip_backend import TamfError, _Arch, _dev_f32, _stream_ptr, hand_side_code, require_gpu
+from ..hip_backend import TamfError, _Arch, _stream_ptr, encoder_batch, require_gpu
 
 BUFFERS = ("classification_token", "hand_side_process.rh_embed", "hand_side_process.lh_embed", "sequence_pos_encoder.pe")
 
@@ -164,25 +164,12 @@ class SegmentEncoderTrainStep:
         dev = self.device
         lab_np = check_labels(labels, self.input_dim)
         self._rebind_moved()
-        side = [hand_side_code(hs) for hs in batch["hand_side"]]
-        pr, sh = _dev_f32(batch["pose_repr"], dev), _dev_f32(batch["shape"], dev)
-        oe, ot = _dev_f32(batch["obj_embedding"], dev), _dev_f32(batch["obj_traj"], dev)
-        B, T, F = pr.shape
-        nobj = ot.shape[1]
-        if F != self.input_dim or tuple(sh.shape[:2]) != (B, T) or tuple(oe.shape[:2]) != (B, nobj) or tuple(ot.shape[:3]) != (B, nobj, T) \
-                or len(side) != B or lab_np.shape != (B,):
-            raise ValueError(f"inconsistent encoder inputs: pose_repr {tuple(pr.shape)}, shape {tuple(sh.shape)}, obj_embedding "
-                             f"{tuple(oe.shape)}, obj_traj {tuple(ot.shape)}, {len(side)} hand sides, {lab_np.shape[0]} labels")
-        num_np = clip_np = None
-        if obj_num is not None:
-            num_np = np.ascontiguousarray(torch.as_tensor(obj_num).cpu().numpy() if isinstance(obj_num, torch.Tensor) else obj_num, dtype=np.int32)
-            if num_np.shape != (B,):
-                raise ValueError(f"obj_num must hold one count per clip: shape {num_np.shape} for B = {B}")
+        (pr, sh, oe, ot), (B, T, F, nobj), num_np, side_d = encoder_batch(batch, obj_num, dev, self.input_dim, n_labels=lab_np.shape[0])
+        clip_np = None
         if clip_ids is not None:
             clip_np = np.ascontiguousarray(torch.as_tensor(clip_ids).cpu().numpy() if isinstance(clip_ids, torch.Tensor) else clip_ids, dtype=np.int64)
             if clip_np.shape != (B,):
                 raise ValueError(f"clip_ids must hold one id per clip: shape {clip_np.shape} for B = {B}")
-        side_d = torch.tensor(side, dtype=torch.uint8, device=dev)
         lab_d = torch.from_numpy(lab_np).to(dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         act = torch.empty(B, F, dtype=torch.float32, device=dev)

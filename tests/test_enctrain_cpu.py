@@ -1,7 +1,10 @@
 """CPU checks of the SegmentEncoder training step's test infrastructure and Python side: the float64 restatement against the
-reference's own module and loss (tests/golden/enctrain_*.npz, captured by tools/capture_enctrain_golden.py), the label check."""
+reference's own module and loss (tests/golden/enctrain_*.npz, captured by tools/capture_enctrain_golden.py), the label check, the
+refusals of the C entry points that come before any device call, and the single place of every state-dict key in the library's source."""
+import ctypes
 import glob
 import os
+import re
 
 import numpy as np
 import pytest
@@ -42,6 +45,73 @@ def test_label_range():
     for bad in ([99], [0, -1], [[0]], [0.5]):
         with pytest.raises(ValueError):
             check_labels(np.asarray(bad), 99)
+
+
+TAMF_ERR_INVALID = -1
+ARCH_FIELDS = ("input_dim", "obj_input_dim", "hand_shape_dim", "obj_embed_dim", "latent_dim", "ff_size", "num_layers", "num_heads")
+HEADS_MSG = "the encoder training step supports latent_dim 64 with 4 heads, got latent_dim %d with %d heads"
+FRAMES_MSG = "max_frames must be in [1, 508] (one head's keys and values in 64 KiB of LDS), got %d"
+
+
+def test_create_and_mask_refusals_through_ctypes():
+    """status and last_error text of every refusal of tamf_enctrain_create and tamf_enctrain_dropout_mask that returns before the
+    first device call; *out, a sentinel before the call, is NULL after every refused create that was given both pointers"""
+    from encoder_restatement import ARCH_ENCODER
+    from oakink2_tamf_amd.hip_backend import _Arch
+    from oakink2_tamf_amd.model import segment_encoder_train as ST
+
+    lib = ST.lib()
+
+    def create(arch=None, max_batch=4, max_frames=28, null=None):
+        a = dict(ARCH_ENCODER, **(arch or {}))
+        st = _Arch(*[int(a[k]) for k in ARCH_FIELDS], 0, 0, 2)
+        out = ctypes.c_void_p(None if null == "arch" else 0x5A5A5A5A)  # (the null check comes before *out is written)
+        rc = lib.tamf_enctrain_create(None if null == "arch" else ctypes.byref(st), max_batch, max_frames, 0, None if null == "out" else ctypes.byref(out))
+        return rc, lib.tamf_enctrain_last_error().decode(), out.value
+
+    for kw, text in ((dict(null="arch"), "null argument"), (dict(null="out"), "null argument"),
+                     (dict(arch=dict(latent_dim=128)), HEADS_MSG % (128, 4)), (dict(arch=dict(num_heads=8)), HEADS_MSG % (64, 8)),
+                     (dict(arch=dict(ff_size=24)), "ff_size must be a multiple of 16 in [16, 512], got 24"),
+                     (dict(arch=dict(ff_size=528)), "ff_size must be a multiple of 16 in [16, 512], got 528"),
+                     (dict(arch=dict(num_layers=0)), "num_layers must be in [1, 64], got 0"),
+                     (dict(arch=dict(num_layers=65)), "num_layers must be in [1, 64], got 65"),
+                     (dict(max_frames=0), FRAMES_MSG % 0), (dict(max_frames=509), FRAMES_MSG % 509),
+                     (dict(max_batch=0), "max_batch must be in [1, 65535], got 0"),
+                     (dict(max_batch=65536), "max_batch must be in [1, 65535], got 65536")):
+        rc, msg, out = create(**kw)
+        assert (rc, msg) == (TAMF_ERR_INVALID, text), (kw, rc, msg)
+        if kw.get("null") != "out":
+            assert out is None, (kw, out)  # *out == NULL
+
+    buf = (ctypes.c_uint8 * 64)()  # never written: the arguments are checked first
+    good = dict(site=0, rows=4, cols=4, p=0.5, out=ctypes.addressof(buf))
+    for kw, text in ((dict(out=None), "null argument"), (dict(rows=0), "rows * cols must be in [1, 2^32)"), (dict(site=-1), "site must be >= 0"),
+                     (dict(p=1.0), "p must be in [0, 1)"), (dict(p=float("nan")), "p must be in [0, 1)")):
+        a = dict(good, **kw)
+        rc = lib.tamf_enctrain_dropout_mask(3, 1, 2, a["site"], a["rows"], a["cols"], a["p"], a["out"], None)
+        assert (rc, lib.tamf_enctrain_last_error().decode()) == (TAMF_ERR_INVALID, text), (kw, rc)
+    assert not any(buf)
+
+
+def test_each_key_is_written_once():
+    """every key stem of the encoder's state dict - outside the layers, and of one layer - occurs exactly once in the text of
+    csrc/tamf_enctrain.hip: where the tensor is declared"""
+    from encoder_restatement import ARCH_ENCODER, seeded_state_dict
+
+    def stem(k):
+        return re.sub(r"\.(weight|bias)$", "", k)
+
+    layer = "seqTransEncoder.layers.0."
+    keys = list(seeded_state_dict(dict(ARCH_ENCODER), 0))
+    outside = sorted({stem(k) for k in keys if not k.startswith("seqTransEncoder.")})
+    per_layer = sorted({stem(k[len(layer):]) for k in keys if k.startswith(layer)})
+    assert len(outside) == 13 and len(per_layer) == 7, (outside, per_layer)  # (norm1 and norm2 are two of the seven)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "oakink2-tamf_amd", "csrc", "tamf_enctrain.hip")) as f:
+        text = f.read()
+    for s in outside + per_layer:  # (as a whole word: input_process.poseEmbedding is also the tail of obj_input_process.poseEmbedding)
+        n = len(re.findall(r"(?<![A-Za-z0-9_.])" + re.escape(s) + r"(?![A-Za-z0-9_])", text))
+        assert n == 1, (s, n)
 
 
 def test_gaussian_perturb_adaptor_equals_reference():
