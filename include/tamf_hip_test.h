@@ -47,6 +47,11 @@ int tamf_test_poke(tamf_ctx* ctx, int32_t alloc_index, int64_t offset, int32_t n
  * TAMF_ERR_NOMEM (n = 0: the next one; -1 disarms).  tests/test_hip_guardbands.py uses it to prove that a tamf_ctx_resize which
  * runs out of memory leaves the context working at its old size. */
 int tamf_test_fail_alloc_after(int32_t n);
+/* Fills every per-step scratch operand of a G / R context - Q | K, the attention output, the hidden activations of the feed-forward
+ * block and the hidden rows of the input merge, each through its current pointer and over its dimensioned size - with `byte` (0 .. 255;
+ * 0xFF is a NaN in every operand format).  The kernels of a step may read only what the same step wrote there: the same call gives the
+ * same bits before and after.  Synchronises the device.  Test hook: no product path calls it. */
+int tamf_test_fill_scratch(tamf_ctx* ctx, int32_t byte);
 /* Philox normal draws exactly as the sampling loop generates them: out (B, n_feat, 1, T). */
 int tamf_test_philox(uint64_t seed, int64_t clip_id_base, int32_t draw, int32_t B, int32_t n_feat, int32_t T,
                      float* out_dev, void* stream);

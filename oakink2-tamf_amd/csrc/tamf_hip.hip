@@ -346,6 +346,26 @@ static int check_dims(const tamf_arch* arch, int max_batch, int max_frames) {
   return 0;
 }
 
+// The views of the hidden operand's allocation (scratch_layout, tamf_launch.h): addresses that depend on (max_batch, max_frames) alone,
+// never on the batch of a call - a captured graph stays valid between calls.  Guard-band mode: the margins between the views get the
+// pattern and a record each, so that tamf_test_check_guards verifies them like an allocation's.
+static int place_scratch_views(tamf_ctx* ctx, const ScratchLayout& sl) {
+  char* host = (char*)ctx->H_op.p;
+  ctx->QK_op.p = host + sl.qk_off;
+  ctx->A_op.p = host + sl.a_off;
+  ctx->h1_op.p = host + sl.h1_off;
+  const size_t guard = g_guard_bytes.load();
+  if (!guard) return 0;
+  const struct { size_t off, bytes; const char* tag; } views[3] = {{(size_t)sl.qk_off, (size_t)sl.qk_bytes, "view QK_op of H_op's allocation"},
+                                                                  {(size_t)sl.a_off, (size_t)sl.a_bytes, "view A_op of H_op's allocation"},
+                                                                  {(size_t)sl.h1_off, (size_t)sl.h1_bytes, "view h1_op of H_op's allocation"}};
+  for (const auto& v : views) {
+    HIPCHK(ctx, hipMemset(host + v.off - guard, GUARD_BYTE, guard));  // (the margin behind a view is the one below the next, or the allocation's own)
+    ctx->guards.push_back(GuardRec{host + v.off - guard, v.bytes, guard, v.tag, true});
+  }
+  return 0;
+}
+
 // every buffer whose size depends on (max_batch, max_frames): sampler state, token rows, operand planes, V^T, scratch
 static int alloc_workspaces(tamf_ctx* ctx, int max_batch, int max_frames) {
   const int d = ctx->d;
@@ -366,14 +386,20 @@ static int alloc_workspaces(tamf_ctx* ctx, int max_batch, int max_frames) {
   if (ctx->prec == TAMF_PREC_F32) ctx->xs_op.p = ctx->xs;
   else { A(alloc_operand(ctx, &ctx->xs_op, BT * ctx->XK, true)); ctx->xs_st = ctx->xs_op.p; }
   A(dev_alloc(ctx, (void**)&ctx->cobj, BT * d * 4));
-  A(alloc_operand(ctx, &ctx->h1_op, BT * d));
+  // Q | K, the attention output and the input-merge rows: views of the hidden operand's allocation where they fit (scratch_layout)
+  const ScratchLayout sl = scratch_layout(Mmax, BT, d, ctx->ff, ctx->EB, g_guard_bytes.load());
+  if (!sl.alias) A(alloc_operand(ctx, &ctx->h1_op, BT * d));
   A(dev_alloc(ctx, (void**)&ctx->X, Mmax * d * 4, true));
   if (ctx->prec == TAMF_PREC_F32) ctx->X_op.p = ctx->X;
   else { A(alloc_operand(ctx, &ctx->X_op, Mmax * d, true)); ctx->X_st = ctx->X_op.p; }
-  A(alloc_operand(ctx, &ctx->QK_op, Mmax * 2 * d, true));
+  if (!sl.alias) A(alloc_operand(ctx, &ctx->QK_op, Mmax * 2 * d, true));
   A(alloc_operand(ctx, &ctx->Vt_op, (long)max_batch * d * Skpmax, true));
-  A(alloc_operand(ctx, &ctx->A_op, Mmax * d, true));
-  A(alloc_operand(ctx, &ctx->H_op, Mmax * ctx->ff, true));
+  if (!sl.alias) A(alloc_operand(ctx, &ctx->A_op, Mmax * d, true));
+  if (!sl.alias) A(alloc_operand(ctx, &ctx->H_op, Mmax * ctx->ff, true));
+  else {
+    A(dev_alloc(ctx, &ctx->H_op.p, sl.host_bytes, true));
+    A(place_scratch_views(ctx, sl));
+  }
   A(dev_alloc(ctx, (void**)&ctx->pstatic, (long)max_batch * ctx->P * d * 4, true));
   A(dev_alloc(ctx, (void**)&ctx->tcur, (long)max_batch * 4, true));
   A(dev_alloc(ctx, (void**)&ctx->status, 16, true));

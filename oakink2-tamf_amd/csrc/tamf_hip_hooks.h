@@ -59,6 +59,24 @@ extern "C" int tamf_test_check_guards(tamf_ctx* ctx, int32_t* n_checked) {
   return 0;
 }
 
+// Every per-step scratch operand of a G / R context (Q | K, attention output, hidden activations, input-merge rows), through its current
+// pointer and over its whole dimensioned size, set to `byte` (0xFF: a NaN in every operand format).  A step whose kernels read only what
+// the same step wrote gives the same bits afterwards (tests/test_scratch_alias_gpu.py).
+extern "C" int tamf_test_fill_scratch(tamf_ctx* ctx, int32_t byte) {
+  TAMF_LAUNCH_LOCK;
+  TRY(need_kind(ctx, __func__, KIND_G | KIND_R));
+  if (byte < 0 || byte > 255) return fail(ctx, TAMF_ERR_INVALID, "byte must be in [0, 255]");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipDeviceSynchronize());
+  const size_t eb = (size_t)ctx->EB, M = (size_t)ctx->Mmax, d = (size_t)ctx->d, BT = (size_t)ctx->Bmax * ctx->Tmax;
+  HIPCHK(ctx, hipMemset(ctx->H_op.p, byte, M * ctx->ff * eb));
+  HIPCHK(ctx, hipMemset(ctx->QK_op.p, byte, M * 2 * d * eb));
+  HIPCHK(ctx, hipMemset(ctx->A_op.p, byte, M * d * eb));
+  HIPCHK(ctx, hipMemset(ctx->h1_op.p, byte, BT * d * eb));
+  HIPCHK(ctx, hipDeviceSynchronize());
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // kernel-level test hooks
 // ------------------------------------------------------------------------------------------------

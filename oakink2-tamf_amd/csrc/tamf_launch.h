@@ -253,6 +253,48 @@ static inline int vt_row_keys(int S, int Sp) {
   return ((S > tile ? S : tile) + 31) / 32 * 32;
 }
 
+// Where the per-layer scratch operands of a context live.  Q | K (Mmax x 2 d), the attention output (Mmax x d) and the input-merge
+// hidden rows (B T x d) are dead before FFN1 writes the hidden activations (Mmax x ff) and the hidden activations are dead before the
+// next QKV launch, on one stream: when Q | K and the attention output fit side by side into the hidden operand they are VIEWS of its
+// allocation (a layer then touches Mmax ff instead of Mmax (ff + 3 d) scratch elements, and an overwrite finds the line it replaces
+// still in the Infinity Cache), and the input-merge rows share the bytes of Q | K.  Otherwise `alias` is false and every buffer is an
+// allocation of its own.  Offsets are bytes from the start of the allocation, multiples of 256.
+//   guard == 0:  [ Q | K ][ attention output ] inside the first hidden_bytes of the allocation; h1 at the offset of Q | K
+//   guard  > 0:  test builds (tamf_test_set_guard_bytes).  FFN1 stores every byte of the hidden operand, so a margin BETWEEN two views
+//                inside it cannot keep a pattern; with margins the views follow the hidden operand in a longer allocation,
+//                [ hidden ] g [ Q | K ] g [ attention output ] g [ h1 ], every g a margin of `guard` pattern bytes (the one behind h1
+//                is the allocation's own) that tamf_test_check_guards verifies: an overrun of a view into its neighbour stays visible.  The decision `alias`
+//                is that of guard == 0, so that a shape takes the same allocation path with and without margins.
+// (plain C++, like clip_tile_rows: tests/test_scratch_layout_cpu.py compiles it on its own)
+struct ScratchLayout {
+  bool alias;
+  unsigned long long host_bytes;  // bytes of the allocation that holds the hidden operand (and, with alias, the views)
+  unsigned long long qk_off, a_off, h1_off;
+  unsigned long long qk_bytes, a_bytes, h1_bytes, hidden_bytes;
+};
+static inline ScratchLayout scratch_layout(long long Mmax, long long BT, int d, int ff, int elem_bytes, unsigned long long guard) {
+  auto up = [](unsigned long long v) { return (v + 255ull) / 256ull * 256ull; };
+  ScratchLayout s{};
+  s.hidden_bytes = up((unsigned long long)Mmax * ff * elem_bytes);
+  s.qk_bytes = up((unsigned long long)Mmax * 2 * d * elem_bytes);
+  s.a_bytes = up((unsigned long long)Mmax * d * elem_bytes);
+  s.h1_bytes = up((unsigned long long)BT * d * elem_bytes);
+  s.host_bytes = s.hidden_bytes;
+  s.alias = s.qk_bytes + s.a_bytes <= s.hidden_bytes && s.h1_bytes <= s.qk_bytes;
+  if (!s.alias) return s;
+  if (guard == 0) {
+    s.qk_off = 0;
+    s.a_off = s.qk_bytes;
+    s.h1_off = 0;
+  } else {
+    s.qk_off = s.hidden_bytes + guard;
+    s.a_off = s.qk_off + s.qk_bytes + guard;
+    s.h1_off = s.a_off + s.a_bytes + guard;
+    s.host_bytes = s.h1_off + s.h1_bytes;  // (the margin behind h1 is the allocation's own)
+  }
+  return s;
+}
+
 // ---- the denoiser step: one selection function per GEMM role ----
 // residual GEMM of the deferred-LayerNorm form (out-proj, FFN2; 16-bit modes): the clip's row parts where whole clips would fill at
 // most half of the CUs, whole-clip tiles where they fill at least half of their rounds' slots, 128 x 128 tiles for every other shape -

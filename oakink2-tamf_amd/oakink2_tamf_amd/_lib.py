@@ -44,7 +44,7 @@ EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
 ]
 HOOK_EXPORTS = [  # include/tamf_hip_test.h: additionally in libtamf_hip_hooks.so
     "tamf_test_gemm", "tamf_test_gemm_resid", "tamf_test_attention", "tamf_test_philox", "tamf_test_set_guard_bytes", "tamf_test_check_guards",
-    "tamf_test_poke", "tamf_test_fail_alloc_after", "tamf_bench_gemm", "tamf_bench_attention", "tamf_bench_mfma_rate", "tamf_set_gemm_tuning",
+    "tamf_test_poke", "tamf_test_fail_alloc_after", "tamf_test_fill_scratch", "tamf_bench_gemm", "tamf_bench_attention", "tamf_bench_mfma_rate", "tamf_set_gemm_tuning",
 ]
 EVAL_EXPORTS = [  # include/tamf_eval.h: what libtamf_eval.so exports
     "tamf_eval_last_error", "tamf_voxelize_lattice", "tamf_mesh_contains_count_workspace", "tamf_mesh_contains_count",

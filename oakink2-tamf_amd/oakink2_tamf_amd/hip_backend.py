@@ -93,6 +93,8 @@ def _bind(L: ctypes.CDLL) -> ctypes.CDLL:
         L.tamf_test_poke.argtypes = [c_void_p, c_int32, c_int64, c_int32]
     if hasattr(L, "tamf_test_fail_alloc_after"):
         L.tamf_test_fail_alloc_after.argtypes = [c_int32]
+    if hasattr(L, "tamf_test_fill_scratch"):
+        L.tamf_test_fill_scratch.argtypes = [c_void_p, c_int32]
     if hasattr(L, "tamf_bench_mfma_rate"):
         L.tamf_bench_mfma_rate.argtypes = [c_int32, c_int32, POINTER(ctypes.c_float), POINTER(ctypes.c_float), c_void_p]
     _bound.add(id(L))
@@ -425,6 +427,12 @@ class TamfContext:
         n = c_int32(0)
         self._check(self._L.tamf_test_check_guards(self._h, ctypes.byref(n)))
         return int(n.value)
+
+    def fill_scratch(self, byte: int = 0xFF) -> None:
+        """Test hook: set every per-step scratch operand of this context (Q | K, attention output, hidden activations, input-merge rows)
+        to `byte`; 0xFF is a NaN in every operand format.  A step reads there only what it wrote itself: results do not change."""
+        with torch.cuda.device(self.device):
+            self._check(self._L.tamf_test_fill_scratch(self._h, int(byte)))
 
     def refine(self, sample_pose_repr: torch.Tensor, h2o_dist: torch.Tensor) -> torch.Tensor:
         dev = self.device
