@@ -25,6 +25,8 @@
 #include "tamf_misc.h"
 #include "tamf_encoder.h"
 #include "tamf_spectrum.h"
+#include "tamf_shapes.h"       // host only: the shape arithmetic
+#include "tamf_weight_prep.h"  // host only: what is uploaded as a weight, before it is uploaded
 
 // run EXPR with `Op` bound to the operand traits of arithmetic mode `prec` (tamf_precision)
 #define TAMF_WITH_OP(prec, EXPR)                                         \
@@ -209,7 +211,6 @@ static int need_kind(tamf_ctx* ctx, const char* func, unsigned mask) {
     if (rc_ != 0) return rc_; \
   } while (0)
 
-static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static inline dim3 grid1d(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
 static std::atomic<int> g_fail_alloc_in{-1};  // test hook (tamf_test_fail_alloc_after): the n-th device allocation from now fails
@@ -238,92 +239,19 @@ static int dev_upload(tamf_ctx* ctx, T** p, const T* host, size_t n) {
   return 0;
 }
 
-// host float -> bf16 (round to nearest even; NaN kept quiet)
-static inline uint16_t h_f2bf(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-static inline float h_bf2f(uint16_t h) {
-  uint32_t u = (uint32_t)h << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
-// upload host fp32 [N][K] as an operand matrix [N][ldk] in precision `prec` (cols >= K zero; ldk % 32 == 0).
-// bf16x3 rows are 128-byte groups of 32 elements: [hi: 32 bf16 | lo: 32 bf16] (tamf_device.h "Operand traits").
+// upload host fp32 [N][K] as an operand matrix [N][ldk] in precision `prec`: packed on the host (pack_operand, tamf_weight_prep.h), its
+// refusal or weight-range note recorded in the context, then uploaded
 static int upload_operand(tamf_ctx* ctx, int prec, const float* w, int N, int K, int ldk, OperandBuf* out, const char* what) {
-  const size_t n = (size_t)N * ldk;
-  if (ldk % 32) return fail(ctx, TAMF_ERR_INVALID, "operand leading dimension must be a multiple of 32");
-  int wexp = 0;  // f16x3: the tensor is stored as w * 2^wexp
-  out->inv_scale = 1.0f;
-  if (prec == TAMF_PREC_F16X3) {
-    // Power-of-two pre-scaling of the split-fp16 weights: max |w| lands in [2^14, 2^15), so that the lo planes of everything down to
-    // 2^-17 of the tensor's maximum are NORMAL fp16 numbers (22 significand bits; unscaled, PyTorch-default weights of ~0.04 had
-    // subnormal lo parts: an absolute 3e-8, i.e. ~19 bits) and a weight beyond the fp16 range is no reason to refuse a checkpoint.
-    // The product is scaled back exactly in the epilogue's bias add (EpiCtl::wscale).  Only a non-finite weight is refused.
-    // (activations are checked on the device: tamf_device.h, status word)
-    float mx = 0.f;
-    for (size_t i = 0; i < (size_t)N * K; ++i) {
-      if (!std::isfinite(w[i]))
-        return fail(ctx, TAMF_ERR_RANGE, std::string("f16x3: weight ") + what + " holds a non-finite value and cannot be stored as split-fp16 operands; use bf16x3 or f32");
-      mx = std::fmax(mx, std::fabs(w[i]));
-    }
-    if (mx > 0.f) {
-      int e = 0;
-      (void)std::frexp(mx, &e);  // mx = m 2^e, m in [0.5, 1)
-      wexp = std::min(120, std::max(-120, 15 - e));
-    }
-    out->inv_scale = std::ldexp(1.0f, -wexp);
-    // One power of two per tensor: a weight smaller than 2^-17.5 of the tensor's maximum has an fp16-SUBNORMAL lo part again (fewer than
-    // 22 significand bits).  Ordinary tensors are nowhere near (max / typical ~ 2^3 .. 2^7); one huge outlier over ordinary weights is
-    // (a single 7e4 among 0.04s leaves the others ~18 bits).  Reported, not refused: a status bit + the tensor's name.
-    size_t small = 0, nonzero = 0;
-    for (size_t i = 0; i < (size_t)N * K; ++i)
-      if (w[i] != 0.f) {
-        ++nonzero;
-        if (std::fabs(std::ldexp(w[i], wexp)) < 0.125f) ++small;
-      }
-    if (nonzero && small * 100 > nonzero) {
-      ctx->host_status |= TAMF_STATUS_F16_WEIGHT_RANGE;
-      if (ctx->weight_note.empty())
-        ctx->weight_note = std::string("f16x3: ") + std::to_string(small * 100 / nonzero) + " % of the non-zero weights of " + what +
-                           " are below 2^-17.5 of the tensor's largest magnitude: stored with fewer than 22 significand bits (an outlier dominates the per-tensor scale)";
-    }
+  const PackedOperand po = pack_operand(prec, w, N, K, ldk);
+  if (po.refused) return fail(ctx, po.error_code(), po.error_message(what));
+  out->inv_scale = po.inv_scale;
+  if (po.small_share_noted()) {
+    ctx->host_status |= TAMF_STATUS_F16_WEIGHT_RANGE;
+    if (ctx->weight_note.empty()) ctx->weight_note = po.range_note(what);
   }
-  if (prec == TAMF_PREC_F32) {
-    std::vector<float> h(n, 0.f);
-    for (int r = 0; r < N; ++r) memcpy(&h[(size_t)r * ldk], &w[(size_t)r * K], (size_t)K * 4);
-    return dev_upload(ctx, (float**)&out->p, h.data(), n);
-  }
-  if (prec == TAMF_PREC_BF16) {
-    std::vector<uint16_t> h(n, 0);
-    for (int r = 0; r < N; ++r)
-      for (int k = 0; k < K; ++k) h[(size_t)r * ldk + k] = h_f2bf(w[(size_t)r * K + k]);
-    return dev_upload(ctx, (uint16_t**)&out->p, h.data(), n);
-  }
-  std::vector<uint16_t> h(n * 2, 0);
-  for (int r = 0; r < N; ++r)
-    for (int k = 0; k < K; ++k) {
-      const float v = w[(size_t)r * K + k];
-      const size_t idx = (size_t)r * ldk + k;
-      const size_t o = (idx >> 5) * 64 + (idx & 31);  // in uint16 units: 64 per 128-byte group
-      if (prec == TAMF_PREC_F16X3) {
-        const float vs = std::ldexp(v, wexp);  // exact
-        const _Float16 hi = (_Float16)vs, lo = (_Float16)(vs - (float)hi);
-        memcpy(&h[o], &hi, 2);
-        memcpy(&h[o + 32], &lo, 2);
-      } else {
-        const uint16_t hi = h_f2bf(v);
-        h[o] = hi;
-        h[o + 32] = h_f2bf(v - h_bf2f(hi));
-      }
-    }
-  return dev_upload(ctx, (uint16_t**)&out->p, h.data(), n * 2);
+  return dev_upload(ctx, (unsigned char**)&out->p, po.image.data(), po.image.size());
 }
+static int upload_vec(tamf_ctx* ctx, float** p, const std::vector<float>& v) { return dev_upload(ctx, p, v.data(), v.size()); }
 
 #include "tamf_launch.h"
 
@@ -339,14 +267,12 @@ static int alloc_operand(tamf_ctx* ctx, OperandBuf* ob, long elems, bool zero = 
 // the kernels address operands with 32-bit byte offsets and int element indices: refuse shapes beyond them
 static int check_dims(const tamf_arch* arch, int max_batch, int max_frames) {
   if (max_batch <= 0 || max_frames <= 0 || max_frames > 4990) return fail(nullptr, TAMF_ERR_INVALID, "bad max_batch/max_frames");
-  const long long sp = (max_frames + 5 + 7) / 8 * 8, mmax = (long long)max_batch * sp;
-  const long long widest = std::max<long long>(arch->ff_size, 3LL * arch->latent_dim);
-  if (mmax * widest * 4 >= (1LL << 32) || (long long)max_batch * max_frames * 896 * 4 >= (1LL << 32))
+  if (!dims_fit_32bit_offsets(max_batch, max_frames, arch->ff_size, arch->latent_dim))
     return fail(nullptr, TAMF_ERR_INVALID, "max_batch x max_frames too large for one context (32-bit operand offsets): split the batch");
   return 0;
 }
 
-// The views of the hidden operand's allocation (scratch_layout, tamf_launch.h): addresses that depend on (max_batch, max_frames) alone,
+// The views of the hidden operand's allocation (scratch_layout, tamf_shapes.h): addresses that depend on (max_batch, max_frames) alone,
 // never on the batch of a call - a captured graph stays valid between calls.  Guard-band mode: the margins between the views get the
 // pattern and a record each, so that tamf_test_check_guards verifies them like an allocation's.
 static int place_scratch_views(tamf_ctx* ctx, const ScratchLayout& sl) {
@@ -369,9 +295,9 @@ static int place_scratch_views(tamf_ctx* ctx, const ScratchLayout& sl) {
 // every buffer whose size depends on (max_batch, max_frames): sampler state, token rows, operand planes, V^T, scratch
 static int alloc_workspaces(tamf_ctx* ctx, int max_batch, int max_frames) {
   const int d = ctx->d;
-  const int Smax = max_frames + ctx->P, Spmax = round_up(Smax, 8), Skpmax = round_up(Smax > 208 ? Smax : 208, 32);  // (>= vt_row_keys of every shape)
+  const SeqShape smax = seq_shape_max(max_frames, ctx->P);  // (Skp >= vt_row_keys of every shape)
   const long BT = (long)max_batch * max_frames;
-  const long Mmax = (long)max_batch * Spmax;
+  const long Mmax = (long)max_batch * smax.Sp;
   ctx->Mmax = Mmax;
   ctx->Bmax = max_batch;
   ctx->Tmax = max_frames;
@@ -393,7 +319,7 @@ static int alloc_workspaces(tamf_ctx* ctx, int max_batch, int max_frames) {
   if (ctx->prec == TAMF_PREC_F32) ctx->X_op.p = ctx->X;
   else { A(alloc_operand(ctx, &ctx->X_op, Mmax * d, true)); ctx->X_st = ctx->X_op.p; }
   if (!sl.alias) A(alloc_operand(ctx, &ctx->QK_op, Mmax * 2 * d, true));
-  A(alloc_operand(ctx, &ctx->Vt_op, (long)max_batch * d * Skpmax, true));
+  A(alloc_operand(ctx, &ctx->Vt_op, (long)max_batch * d * smax.Skp, true));
   if (!sl.alias) A(alloc_operand(ctx, &ctx->A_op, Mmax * d, true));
   if (!sl.alias) A(alloc_operand(ctx, &ctx->H_op, Mmax * ctx->ff, true));
   else {
@@ -492,8 +418,6 @@ static int gr_prepare(tamf_ctx* ctx) {  // workgroup slots of the device, kernel
   return 0;
 }
 
-static std::map<std::string, std::vector<int64_t>> expected_shapes(const tamf_ctx* c);
-
 extern "C" int tamf_ctx_create(const tamf_arch* arch, int32_t max_batch, int32_t max_frames, int32_t precision,
                                int32_t device, tamf_ctx** out) {
   if (!arch || !out) return fail(nullptr, TAMF_ERR_INVALID, "null argument");
@@ -525,11 +449,11 @@ extern "C" int tamf_ctx_create(const tamf_arch* arch, int32_t max_batch, int32_t
     ctx->P = ENC_P;
     ctx->enc_kin = round_up(arch->input_dim + arch->obj_input_dim, 4);
   } else {
-    ctx->P = arch->kind == TAMF_KIND_G ? 5 : 3;
+    ctx->P = arch->kind == TAMF_KIND_G ? PREFIX_ROWS_G : PREFIX_ROWS_R;
     ctx->XK = arch->kind == TAMF_KIND_G ? 128 : round_up(arch->input_dim + arch->h2o_dim, 64);
     ctx->layers.resize(ctx->L);
   }
-  ctx->expected = expected_shapes(ctx);
+  ctx->expected = expected_shapes(ctx->arch);
 
   auto bail = [&](int rc) {
     std::string e = ctx->err;
@@ -632,54 +556,6 @@ extern "C" int tamf_ctx_resize(tamf_ctx* ctx, int32_t max_batch, int32_t max_fra
 // ------------------------------------------------------------------------------------------------
 // weights
 // ------------------------------------------------------------------------------------------------
-// the state-dict key set of the context's kind (SegmentEncoder: segment_encoder.py:16-75) with the shape of every tensor
-static std::map<std::string, std::vector<int64_t>> expected_shapes(const tamf_ctx* c) {
-  std::map<std::string, std::vector<int64_t>> m;
-  const int64_t d = c->d, ff = c->ff;
-  const int kind = c->arch.kind;
-  auto lin = [&](const std::string& n, int64_t o, int64_t i) {
-    m[n + ".weight"] = {o, i};
-    m[n + ".bias"] = {o};
-  };
-  m["hand_side_process.rh_embed"] = {d};
-  m["hand_side_process.lh_embed"] = {d};
-  lin("hand_shape_process.shape_embed", d, c->arch.hand_shape_dim);
-  lin("obj_embed_process.embedding", d, c->arch.obj_embed_dim);
-  lin("input_process.poseEmbedding", d, c->arch.input_dim);
-  lin("obj_input_process.poseEmbedding", d, c->arch.obj_input_dim);
-  lin("input_merge.0", d, (kind == TAMF_KIND_R ? 3 : 2) * d);
-  lin("input_merge.2", d, d);
-  m["sequence_pos_encoder.pe"] = {5000, 1, d};
-  for (int l = 0; l < c->L; ++l) {
-    const std::string p = "seqTransEncoder.layers." + std::to_string(l);
-    m[p + ".self_attn.in_proj_weight"] = {3 * d, d};
-    m[p + ".self_attn.in_proj_bias"] = {3 * d};
-    lin(p + ".self_attn.out_proj", d, d);
-    lin(p + ".linear1", ff, d);
-    lin(p + ".linear2", d, ff);
-    m[p + ".norm1.weight"] = {d};
-    m[p + ".norm1.bias"] = {d};
-    m[p + ".norm2.weight"] = {d};
-    m[p + ".norm2.bias"] = {d};
-  }
-  if (kind == TAMF_KIND_E) {
-    m["classification_token"] = {1, 1, d};
-    lin("output_process.poseFinal.0", d, d);
-    lin("output_process.poseFinal.2", d, d);
-    lin("output_process.poseFinal.4", c->arch.input_dim, d);
-    return m;
-  }
-  if (kind == TAMF_KIND_R) {
-    lin("h2o_dist_input_process.poseEmbedding", d, c->arch.h2o_dim);
-  } else {
-    lin("embed_timestep.time_embed.0", d, d);
-    lin("embed_timestep.time_embed.2", d, d);
-    lin("embed_text", d, c->arch.clip_dim);
-  }
-  lin("output_process.poseFinal", c->arch.input_dim, d);
-  return m;
-}
-
 extern "C" int tamf_load_weight(tamf_ctx* ctx, const char* name, const float* host_data, const int64_t* shape,
                                 int32_t ndim) {
   if (!ctx || !name || !host_data || !shape || ndim <= 0) return fail(ctx, TAMF_ERR_INVALID, "null/invalid argument");
@@ -699,11 +575,7 @@ static int upload_f32(tamf_ctx* ctx, const std::string& name, float** p) {
   return dev_upload(ctx, p, v.data(), v.size());
 }
 static int upload_T(tamf_ctx* ctx, const std::string& name, int N, int K, float** p) {  // W [N][K] -> W^T [K][N] (prefix_rows_kernel)
-  const float* W = ctx->raw.at(name).data();
-  std::vector<float> t((size_t)N * K);
-  for (int n = 0; n < N; ++n)
-    for (int k = 0; k < K; ++k) t[(size_t)k * N + n] = W[(size_t)n * K + k];
-  return dev_upload(ctx, p, t.data(), t.size());
+  return upload_vec(ctx, p, transposed(ctx->raw.at(name).data(), N, K));
 }
 // the tables of the prefix rows that every kind has (prefix_rows_kernel): hand shape, object embedding, hand side
 static int upload_prefix_tables(tamf_ctx* ctx) {
@@ -715,18 +587,6 @@ static int upload_prefix_tables(tamf_ctx* ctx) {
   TRY(upload_f32(ctx, "hand_side_process.rh_embed", &ctx->rh));
   return upload_f32(ctx, "hand_side_process.lh_embed", &ctx->lh);
 }
-// One block of the composed input map, in float64: out[n * ld_n + k * ld_k] = sum_j W_m1[n][col0 + j] W_x[j][k] (n, j < d; k < K), where
-// W_m1 = input_merge.0.weight [d][mk] and W_x [d][K] is the embedding that feeds its columns col0 .. col0 + d.  ld_k = 1: row-major
-// rows of the fused weight; ld_n = 1: transposed (WcT of cobj_kernel).
-static void compose_block(const float* Wm1, int mk, int col0, int d, const float* Wx, int K, float* out, long ld_n, long ld_k) {
-  for (int n = 0; n < d; ++n)
-    for (int k = 0; k < K; ++k) {
-      double a = 0;
-      for (int j = 0; j < d; ++j) a += (double)Wm1[(size_t)n * mk + col0 + j] * Wx[(size_t)j * K + k];
-      out[n * ld_n + k * ld_k] = (float)a;
-    }
-}
-
 // SegmentEncoder weights -> the packed layout of tamf_encoder.h (EncHeadOff, then one EncLayerOff block per layer) + the prefix-row
 // tables of prefix_rows_kernel.  The input linear maps are composed in float64 as for G / R: W_in = [W_m1[:, :d] W_p | W_m1[:, d:] W_q].
 static int enc_finalize(tamf_ctx* ctx) {
@@ -741,11 +601,7 @@ static int enc_finalize(tamf_ctx* ctx) {
     const float *Wm1 = R("input_merge.0.weight"), *bm1 = R("input_merge.0.bias");
     const float *Wp = R("input_process.poseEmbedding.weight"), *bp = R("input_process.poseEmbedding.bias");
     const float *Wq = R("obj_input_process.poseEmbedding.weight"), *bq = R("obj_input_process.poseEmbedding.bias");
-    for (int n = 0; n < d; ++n) {
-      double acc_b = bm1[n];
-      for (int j = 0; j < d; ++j) acc_b += (double)Wm1[(size_t)n * 2 * d + j] * bp[j] + (double)Wm1[(size_t)n * 2 * d + d + j] * bq[j];
-      w[ho.bin + n] = (float)acc_b;
-    }
+    input_bias_two_terms_per_column(Wm1, d, bm1, bp, bq, w.data() + ho.bin);
     compose_block(Wm1, 2 * d, 0, d, Wp, F, w.data() + ho.win, kin, 1);
     compose_block(Wm1, 2 * d, d, d, Wq, qd, w.data() + ho.win + F, kin, 1);
   }
@@ -806,25 +662,19 @@ extern "C" int tamf_finalize_weights(tamf_ctx* ctx, int32_t max_timesteps, void*
   }
   const int d = ctx->d, ff = ctx->ff, F = ctx->F, prec = ctx->prec;
   auto R = [&](const std::string& n) -> const float* { return ctx->raw.at(n).data(); };
-  // Deferred LayerNorm: fold the gain AND the centring of the LayerNorm in front of a GEMM into its weight, W'' = W diag(gamma) (I - 1 1^T / d)
-  // (fp64: every row of W diag(gamma) minus its own mean), c2 = W beta + bias; the residual adds take gamma and beta + bias of the
-  // LayerNorm their residual input passes through.  W is [N][d]; the uploaded operand and c2 have Npad >= N rows, zero beyond N (the
-  // output head).  g = be = null (layer 0's attention block reads the encoder input itself): the plain weight.
-  auto fold = [&](const float* W, const float* bias, int N, int Npad, const float* g, const float* be, OperandBuf* ob, float** c2,
-                  const std::string& what) -> int {
-    std::vector<float> wf((size_t)Npad * d, 0.f), v2(Npad, 0.f);
-    for (int n = 0; n < N; ++n) {
-      double acc = bias[n], rowsum = 0.0;
-      for (int k = 0; k < d; ++k) {
-        if (g) rowsum += (double)W[(size_t)n * d + k] * g[k];
-        if (be) acc += (double)W[(size_t)n * d + k] * be[k];
-      }
-      const double shift = g ? rowsum / d : 0.0;  // W'' = W diag(gamma) (I - 1 1^T / d): every row minus its own mean
-      for (int k = 0; k < d; ++k) wf[(size_t)n * d + k] = g ? (float)((double)W[(size_t)n * d + k] * g[k] - shift) : W[(size_t)n * d + k];
-      v2[n] = (float)acc;
-    }
-    TRY(upload_operand(ctx, prec, wf.data(), Npad, d, d, ob, what.c_str()));
-    return dev_upload(ctx, c2, v2.data(), v2.size());
+  // a linear map [N][d] behind a deferred LayerNorm (gamma g, beta be; null: none): the folded weight as an operand of Npad rows, c2 in
+  // place of its bias (fold_layernorm, tamf_weight_prep.h)
+  auto upload_folded = [&](const std::string& weight, const std::string& bias, int N, int Npad, const float* g, const float* be, OperandBuf* ob,
+                           float** c2) -> int {
+    const FoldedLinear f = fold_layernorm(R(weight), R(bias), N, Npad, d, g, be);
+    TRY(upload_operand(ctx, prec, f.w.data(), Npad, d, d, ob, weight.c_str()));
+    return upload_vec(ctx, c2, f.c2);
+  };
+  // what the residual add behind a block takes: gamma, beta + the bias of the block's last linear map (residual_ln)
+  auto upload_residual_ln = [&](const float* g, const float* be, const std::string& bias, float** g_dev, float** bb_dev) -> int {
+    const ResidualLn r = residual_ln(g, be, R(bias), d);
+    TRY(upload_vec(ctx, g_dev, r.g));
+    return upload_vec(ctx, bb_dev, r.bb);
   };
 
   for (int l = 0; l < ctx->L; ++l) {
@@ -836,61 +686,31 @@ extern "C" int tamf_finalize_weights(tamf_ctx* ctx, int32_t max_timesteps, void*
       const float* be_in = l ? R(pp + ".norm2.bias") : nullptr;
       const float* g1 = R(p + ".norm1.weight");                    // ... in front of its feed-forward block
       const float* be1 = R(p + ".norm1.bias");
-      TRY(fold(R(p + ".self_attn.in_proj_weight"), R(p + ".self_attn.in_proj_bias"), 3 * d, 3 * d, g_in, be_in, &w.Win, &w.c2_in,
-               p + ".self_attn.in_proj_weight"));
-      TRY(fold(R(p + ".linear1.weight"), R(p + ".linear1.bias"), ff, ff, g1, be1, &w.W1, &w.c2_ff, p + ".linear1.weight"));
-      std::vector<float> ga(d), bb(d);
-      for (int n = 0; n < d; ++n) {
-        ga[n] = g_in ? g_in[n] : 1.0f;
-        bb[n] = (be_in ? be_in[n] : 0.0f) + R(p + ".self_attn.out_proj.bias")[n];
-      }
-      TRY(dev_upload(ctx, &w.g_att, ga.data(), ga.size()));
-      TRY(dev_upload(ctx, &w.bb_att, bb.data(), bb.size()));
-      for (int n = 0; n < d; ++n) {
-        ga[n] = g1[n];
-        bb[n] = be1[n] + R(p + ".linear2.bias")[n];
-      }
-      TRY(dev_upload(ctx, &w.g_ffn, ga.data(), ga.size()));
-      TRY(dev_upload(ctx, &w.bb_ffn, bb.data(), bb.size()));
+      TRY(upload_folded(p + ".self_attn.in_proj_weight", p + ".self_attn.in_proj_bias", 3 * d, 3 * d, g_in, be_in, &w.Win, &w.c2_in));
+      TRY(upload_folded(p + ".linear1.weight", p + ".linear1.bias", ff, ff, g1, be1, &w.W1, &w.c2_ff));
+      TRY(upload_residual_ln(g_in, be_in, p + ".self_attn.out_proj.bias", &w.g_att, &w.bb_att));
+      TRY(upload_residual_ln(g1, be1, p + ".linear2.bias", &w.g_ffn, &w.bb_ffn));
     }
     TRY(upload_operand(ctx, prec, R(p + ".self_attn.out_proj.weight"), d, d, d, &w.Wout, (p + ".self_attn.out_proj.weight").c_str()));
     TRY(upload_operand(ctx, prec, R(p + ".linear2.weight"), d, ff, ff, &w.W2, (p + ".linear2.weight").c_str()));
   }
-  // fused input weight: input_merge.0[:, :d] . poseEmbedding (and, for R, input_merge.0[:, 2d:] . h2o embedding)
-  {
+  {  // fused input weight: input_merge.0[:, :d] . poseEmbedding (and, for R, input_merge.0[:, 2d:] . h2o embedding), its object half, its bias
     const bool isR = ctx->arch.kind == TAMF_KIND_R;
-    const int mk = isR ? 3 * d : 2 * d;
-    const float* Wm1 = R("input_merge.0.weight");
-    const float* bm1 = R("input_merge.0.bias");
-    const float* Wp = R("input_process.poseEmbedding.weight");
-    const float* bp = R("input_process.poseEmbedding.bias");
-    const int qd = ctx->arch.obj_input_dim;
-    const float* Wq = R("obj_input_process.poseEmbedding.weight");
-    const float* bq = R("obj_input_process.poseEmbedding.bias");
-    const float* bh = isR ? R("h2o_dist_input_process.poseEmbedding.bias") : nullptr;
-    std::vector<float> fused((size_t)d * ctx->XK, 0.f), cb(d), wct((size_t)qd * d);
-    for (int n = 0; n < d; ++n) {  // the bias: one term after the other (the encoder adds its two inside one loop: not shared)
-      double acc_b = bm1[n];
-      for (int j = 0; j < d; ++j) acc_b += (double)Wm1[(size_t)n * mk + j] * bp[j];
-      for (int j = 0; j < d; ++j) acc_b += (double)Wm1[(size_t)n * mk + d + j] * bq[j];
-      if (isR)
-        for (int j = 0; j < d; ++j) acc_b += (double)Wm1[(size_t)n * mk + 2 * d + j] * bh[j];
-      cb[n] = (float)acc_b;
-    }
-    compose_block(Wm1, mk, 0, d, Wp, F, fused.data(), ctx->XK, 1);
-    // the object half, hoisted out of the loop (cobj_kernel): W_m1[:, d:2d] . (W_q m + b_q) = Wc m + ..., Wc = W_m1[:, d:2d] . W_q
-    compose_block(Wm1, mk, d, d, Wq, qd, wct.data(), 1, d);
-    if (isR) compose_block(Wm1, mk, 2 * d, d, R("h2o_dist_input_process.poseEmbedding.weight"), ctx->arch.h2o_dim, fused.data() + F, ctx->XK, 1);
-    TRY(upload_operand(ctx, prec, fused.data(), d, ctx->XK, ctx->XK, &ctx->Wfused, "input_merge.0.weight x poseEmbedding.weight (fused)"));
-    TRY(dev_upload(ctx, &ctx->WcT, wct.data(), wct.size()));
-    TRY(dev_upload(ctx, &ctx->bc, cb.data(), cb.size()));
+    const FusedInput fi = fuse_input(d, F, ctx->arch.obj_input_dim, ctx->arch.h2o_dim, ctx->XK, R("input_merge.0.weight"), R("input_merge.0.bias"),
+                                     R("input_process.poseEmbedding.weight"), R("input_process.poseEmbedding.bias"),
+                                     R("obj_input_process.poseEmbedding.weight"), R("obj_input_process.poseEmbedding.bias"),
+                                     isR ? R("h2o_dist_input_process.poseEmbedding.weight") : nullptr,
+                                     isR ? R("h2o_dist_input_process.poseEmbedding.bias") : nullptr);
+    TRY(upload_operand(ctx, prec, fi.w.data(), d, ctx->XK, ctx->XK, &ctx->Wfused, "input_merge.0.weight x poseEmbedding.weight (fused)"));
+    TRY(upload_vec(ctx, &ctx->WcT, fi.wct));
+    TRY(upload_vec(ctx, &ctx->bc, fi.bias));
   }
   TRY(upload_operand(ctx, prec, R("input_merge.2.weight"), d, d, d, &ctx->Wm2, "input_merge.2.weight"));
   TRY(upload_f32(ctx, "input_merge.2.bias", &ctx->bm2));
   {  // the encoder's last LayerNorm, deferred into the head: W_f diag(gamma) (I - 1 1^T / d), c2 = W_f beta + b_f; XN rows, zero beyond F
     const std::string pl = "seqTransEncoder.layers." + std::to_string(ctx->L - 1);
-    TRY(fold(R("output_process.poseFinal.weight"), R("output_process.poseFinal.bias"), F, ctx->XN, R(pl + ".norm2.weight"), R(pl + ".norm2.bias"),
-             &ctx->Wf, &ctx->bf, "output_process.poseFinal.weight"));
+    TRY(upload_folded("output_process.poseFinal.weight", "output_process.poseFinal.bias", F, ctx->XN, R(pl + ".norm2.weight"), R(pl + ".norm2.bias"),
+                      &ctx->Wf, &ctx->bf));
   }
   TRY(upload_f32(ctx, "sequence_pos_encoder.pe", &ctx->pe));
   if (ctx->arch.hand_shape_dim > 64 || ctx->arch.obj_input_dim > COBJ_QMAX || d > 1024)
@@ -1051,10 +871,11 @@ extern "C" int tamf_set_cond_ragged(tamf_ctx* ctx, int32_t B, int32_t T, int32_t
   const int d = ctx->d, P = ctx->P, ht = ctx->has_t, nrows = P - ht;
   ctx->B = B;
   ctx->T = T;
-  ctx->S = T + P;
-  ctx->Sp = round_up(ctx->S, 8);
-  ctx->Skp = vt_row_keys(ctx->S, ctx->Sp);
-  ctx->M = B * ctx->Sp;
+  const SeqShape sq = seq_shape(T, P);
+  ctx->S = sq.S;
+  ctx->Sp = sq.Sp;
+  ctx->Skp = sq.Skp;
+  ctx->M = B * sq.Sp;
   ctx->cond_set = false;
   HIPCHK(ctx, hipMemcpyAsync(ctx->side_dev, hand_side_host, B, hipMemcpyHostToDevice, st));
   // two launches (tamf_misc.h): the static prefix rows of every clip, and the hoisted object half of input_merge.0 per frame

@@ -1,7 +1,9 @@
 // Which kernel runs a GEMM or attention launch of a given shape, with what grid / block / LDS size: the selection words, the launcher
 // of every kernel family, one selection function per GEMM role of the denoiser step, the attention launch, and prepare_all.  Host
 // code; tamf_hip.hip includes it after the kernel headers.  Nothing here knows tamf_ctx: operands, epilogues and shapes come in.
+// The shape arithmetic the decisions rest on (clip_tile_rows, vt_row_keys, scratch_layout, ...) is HIP-free and lives in tamf_shapes.h.
 #pragma once
+#include "tamf_shapes.h"
 // ------------------------------------------------------------------------------------------------
 // kernel launchers
 // ------------------------------------------------------------------------------------------------
@@ -213,21 +215,11 @@ struct ClipLaunch {
     return whole * 2 <= cus;
   }
 };
-// The clip lengths that have clip tiles, written here and nowhere else: rows of the whole-clip tile (13 or 11 row tiles of 16) that
-// holds a clip of Sp padded rows, 0 for a length without one.  (plain C++, like vt_row_keys below: tests/test_host_mirror.py compiles
-// the two on their own)
-static inline int clip_tile_rows(int Sp) { return (Sp > 176 && Sp <= 208) ? 208 : (Sp > 144 && Sp <= 176) ? 176 : 0; }
-// ... and for the kernel-level hooks, which take M rows and no clip length: the padded rows per clip when M is whole clips of
-// T = 196 (208 rows) or of T = 160 (168 rows), else 0
-static inline int clip_rows_of_m(int M) { return M % 208 == 0 ? 208 : (M % 168 == 0 ? 168 : 0); }
 // Bind NS (whole-clip row tiles: 13 or 11) and NSP (row tiles of the first of two row parts: 7 or 6) for a clip of Sp padded rows
 // and run the statement(s) that follow Sp_ (variadic: template argument lists carry commas); nothing runs for other clip lengths
 #define TAMF_CLIP_NSUB(Sp_, ...)                                                                                  \
   if (clip_tile_rows(Sp_) == 13 * 16) { constexpr int NS = 13, NSP = 7; (void)NSP; (void)NS; __VA_ARGS__; }      \
   else if (clip_tile_rows(Sp_) == 11 * 16) { constexpr int NS = 11, NSP = 6; (void)NSP; (void)NS; __VA_ARGS__; }
-
-// share of the workgroup slots of its rounds that a launch of `tiles` workgroups uses
-static inline double round_util(int tiles, int slots) { return (double)tiles / (double)(((tiles + slots - 1) / slots) * slots); }
 
 // 128 x 128 tiles, or 64 x 128 tiles (8 waves) for the short-K launches that fill at most half of the workgroup slots (the
 // input-merge GEMMs at <= 32 clips: 20.7 against 23.4 us at B = 32).  Measured and left on the big tiles: QKV (624 tiles at
@@ -243,56 +235,6 @@ static hipError_t gemm128(const GemmArgs<Op>& ga, const Epi& epi, hipStream_t st
       return GemmLaunch<Op, 64, 128, Epi>::launch(ga, epi, st);
   }
   return GemmLaunch<Op, 128, 128, Epi, EpiCanSplit<Epi>::value>::launch(ga, epi, st);
-}
-
-// Keys per V^T row (the row stride of Vt_op): the sequence rounded up to whole 32-key blocks - and at least the rows of the clip tile
-// that writes V^T in f32 (EpiVt stores every row tile of its 208- / 176-row tile, zeros past the clip: T = 174 is S = 179, 192 keys in
-// blocks, but 13 row tiles = 208 stored positions - they ran into the next feature's row and, for the last one, past the buffer)
-static inline int vt_row_keys(int S, int Sp) {
-  const int tile = clip_tile_rows(Sp);
-  return ((S > tile ? S : tile) + 31) / 32 * 32;
-}
-
-// Where the per-layer scratch operands of a context live.  Q | K (Mmax x 2 d), the attention output (Mmax x d) and the input-merge
-// hidden rows (B T x d) are dead before FFN1 writes the hidden activations (Mmax x ff) and the hidden activations are dead before the
-// next QKV launch, on one stream: when Q | K and the attention output fit side by side into the hidden operand they are VIEWS of its
-// allocation (a layer then touches Mmax ff instead of Mmax (ff + 3 d) scratch elements, and an overwrite finds the line it replaces
-// still in the Infinity Cache), and the input-merge rows share the bytes of Q | K.  Otherwise `alias` is false and every buffer is an
-// allocation of its own.  Offsets are bytes from the start of the allocation, multiples of 256.
-//   guard == 0:  [ Q | K ][ attention output ] inside the first hidden_bytes of the allocation; h1 at the offset of Q | K
-//   guard  > 0:  test builds (tamf_test_set_guard_bytes).  FFN1 stores every byte of the hidden operand, so a margin BETWEEN two views
-//                inside it cannot keep a pattern; with margins the views follow the hidden operand in a longer allocation,
-//                [ hidden ] g [ Q | K ] g [ attention output ] g [ h1 ], every g a margin of `guard` pattern bytes (the one behind h1
-//                is the allocation's own) that tamf_test_check_guards verifies: an overrun of a view into its neighbour stays visible.  The decision `alias`
-//                is that of guard == 0, so that a shape takes the same allocation path with and without margins.
-// (plain C++, like clip_tile_rows: tests/test_scratch_layout_cpu.py compiles it on its own)
-struct ScratchLayout {
-  bool alias;
-  unsigned long long host_bytes;  // bytes of the allocation that holds the hidden operand (and, with alias, the views)
-  unsigned long long qk_off, a_off, h1_off;
-  unsigned long long qk_bytes, a_bytes, h1_bytes, hidden_bytes;
-};
-static inline ScratchLayout scratch_layout(long long Mmax, long long BT, int d, int ff, int elem_bytes, unsigned long long guard) {
-  auto up = [](unsigned long long v) { return (v + 255ull) / 256ull * 256ull; };
-  ScratchLayout s{};
-  s.hidden_bytes = up((unsigned long long)Mmax * ff * elem_bytes);
-  s.qk_bytes = up((unsigned long long)Mmax * 2 * d * elem_bytes);
-  s.a_bytes = up((unsigned long long)Mmax * d * elem_bytes);
-  s.h1_bytes = up((unsigned long long)BT * d * elem_bytes);
-  s.host_bytes = s.hidden_bytes;
-  s.alias = s.qk_bytes + s.a_bytes <= s.hidden_bytes && s.h1_bytes <= s.qk_bytes;
-  if (!s.alias) return s;
-  if (guard == 0) {
-    s.qk_off = 0;
-    s.a_off = s.qk_bytes;
-    s.h1_off = 0;
-  } else {
-    s.qk_off = s.hidden_bytes + guard;
-    s.a_off = s.qk_off + s.qk_bytes + guard;
-    s.h1_off = s.a_off + s.a_bytes + guard;
-    s.host_bytes = s.h1_off + s.h1_bytes;  // (the margin behind h1 is the allocation's own)
-  }
-  return s;
 }
 
 // ---- the denoiser step: one selection function per GEMM role ----

@@ -283,7 +283,7 @@ def test_clip_tiles_over_the_clip_lengths_they_accept(prec, B, arch_name, test_h
     """27 clip lengths between T = 139 and 204 (every fourth one plus the edges of the tile families; Sp = 144 .. 216: below, inside and
     above the 176- / 208-row clip tiles and their row parts): the default kernels against the 128 x 128 tiles (selection 1: no clip
     tiles at all) - the same bits - and finite.  (T = 172 .. 187 and 140 .. 155 used to run the f32 V^T clip tile past the V^T rows:
-    vt_row_keys, csrc/tamf_launch.h.  A comparison of kernels with kernels cannot see a store that lands in a neighbouring live buffer;
+    vt_row_keys, csrc/tamf_shapes.h.  A comparison of kernels with kernels cannot see a store that lands in a neighbouring live buffer;
     EVERY length 1 .. 224 is walked by tests/test_hip_guardbands.py with guard bands around every allocation.)"""
     from oracle import mdm_oracle as O
     from oakink2_tamf_amd.hip_backend import lib

@@ -130,10 +130,10 @@ def _function_text(src, signature):
 
 def test_launch_selection_is_in_one_header():
     """csrc/tamf_launch.h decides every GEMM / attention launch: the step names its GEMMs and no launcher, one place sets the dynamic-LDS
-    attribute, one function knows the clip lengths that have clip tiles"""
+    attribute, one function (of csrc/tamf_shapes.h, which it includes) knows the clip lengths that have clip tiles"""
     from oakink2_tamf_amd import _lib
 
-    assert "tamf_launch.h" in _lib.SAMPLER.sources
+    assert "tamf_launch.h" in _lib.SAMPLER.sources and "tamf_shapes.h" in _lib.SAMPLER.sources
     step = _function_text(_csrc("tamf_hip.hip"), "static int enqueue_step(")
     assert step.rstrip().endswith("return 0;\n}") and "gemm_head_ddpm" in step  # (the whole body)
     for word in ("ClipLaunch<", "GemmLaunch<", "GemmDeepLaunch<", "TAMF_CLIP_NSUB"):
@@ -143,14 +143,15 @@ def test_launch_selection_is_in_one_header():
     assert "hipFuncAttributeMaxDynamicSharedMemorySize" in _function_text(three["tamf_launch.h"], "static hipError_t lds_once(")
     # 176 as a bound of a clip length: a comparison of something named Sp / Sp_ / sp with it, in either order
     bound = re.compile(r"\b[Ss]p_?\)?\s*(?:<=|>=|<|>|==)\s*\(?176\b|\b176\)?\s*(?:<=|>=|<|>|==)\s*\(?[Ss]p_?\b")
-    table = _function_text(three["tamf_launch.h"], "static inline int clip_tile_rows(int Sp)")
+    four = dict(three, **{"tamf_shapes.h": _csrc("tamf_shapes.h")})
+    table = _function_text(four["tamf_shapes.h"], "static inline int clip_tile_rows(int Sp)")
     assert len(bound.findall(table)) == 2  # (176, 208] and (144, 176]
-    for name, text in three.items():
+    for name, text in four.items():
         assert not bound.findall(text.replace(table, "")), name
 
 
 def test_clip_length_table_and_vt_row_keys(tmp_path):
-    """clip_tile_rows and vt_row_keys (csrc/tamf_launch.h) compiled on their own, as the plain host functions they are: the table against
+    """clip_tile_rows and vt_row_keys (csrc/tamf_shapes.h, included by a stand-alone program: plain host code): the table against
     the ranges written out here, and a V^T row that holds both the sequence and every row of the clip tile that writes it, in whole
     32-key blocks"""
     import shutil
@@ -158,19 +159,19 @@ def test_clip_length_table_and_vt_row_keys(tmp_path):
 
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     assert cxx, "no host C++ compiler"
-    hdr = _csrc("tamf_launch.h")
+    from oakink2_tamf_amd import _lib
+
     main = r"""
 #include <cstdio>
-%s
-%s
+#include "tamf_shapes.h"
 int main() {
-  for (int Sp = 8; Sp <= 224; Sp += 8) printf("t %%d %%d\n", Sp, clip_tile_rows(Sp));
-  for (int S = 1; S <= 224; ++S) printf("k %%d %%d\n", S, vt_row_keys(S, (S + 7) / 8 * 8));
+  for (int Sp = 8; Sp <= 224; Sp += 8) printf("t %d %d\n", Sp, clip_tile_rows(Sp));
+  for (int S = 1; S <= 224; ++S) printf("k %d %d\n", S, vt_row_keys(S, (S + 7) / 8 * 8));
   return 0;
 }
-""" % (_function_text(hdr, "static inline int clip_tile_rows(int Sp)"), _function_text(hdr, "static inline int vt_row_keys(int S, int Sp)"))
+"""
     (tmp_path / "m.cpp").write_text(main)
-    subprocess.run([cxx, "-std=c++17", "-O0", "-o", str(tmp_path / "m"), str(tmp_path / "m.cpp")], check=True)
+    subprocess.run([cxx, "-std=c++17", "-O0", "-I", _lib.CSRC, "-o", str(tmp_path / "m"), str(tmp_path / "m.cpp")], check=True)
     out = subprocess.run([str(tmp_path / "m")], check=True, capture_output=True, text=True).stdout.split("\n")
     rows = {int(l.split()[1]): int(l.split()[2]) for l in out if l.startswith("t ")}
     keys = {int(l.split()[1]): int(l.split()[2]) for l in out if l.startswith("k ")}

@@ -1,7 +1,7 @@
 """GPU: the per-step scratch operands (Q | K, attention output, hidden activations, input-merge rows) hold nothing that a step needs
 from an earlier one - whichever bytes they share.
 
-scratch_layout (csrc/tamf_launch.h) makes Q | K, the attention output and the input-merge rows views of the hidden operand's allocation
+scratch_layout (csrc/tamf_shapes.h) makes Q | K, the attention output and the input-merge rows views of the hidden operand's allocation
 when ff >= 3 d.  What used to be allocation-time zeros beyond the rows a call writes - the clips between a call's batch and max_batch,
 the clamped rows of a partial row tile (T = 160: 168 padded rows on 176-row tiles) - is then the data of another operand.  Here the
 smallest architecture that aliases (d = 128, ff = 512, two heads, two layers: layer 2's QKV overwrites layer 1's hidden rows) runs

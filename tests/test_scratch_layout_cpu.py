@@ -1,7 +1,7 @@
-"""CPU: scratch_layout (csrc/tamf_launch.h) - where Q | K, the attention output and the input-merge rows of a sampler context live:
-views of the hidden operand's allocation when they fit, allocations of their own otherwise.  Compiled on its own, as the plain host
-function it is, and checked over the architectures (d, ff), the operand widths, guard-band mode and every context size from one clip
-of one frame to 64 clips of 208 rows."""
+"""CPU: scratch_layout (csrc/tamf_shapes.h) - where Q | K, the attention output and the input-merge rows of a sampler context live:
+views of the hidden operand's allocation when they fit, allocations of their own otherwise.  A stand-alone program includes the
+header (plain host code); checked over the architectures (d, ff), the operand widths, guard-band mode and every context size from one
+clip of one frame to 64 clips of 208 rows."""
 import os
 import shutil
 import subprocess
@@ -10,21 +10,6 @@ import pytest
 
 from conftest import ROOT
 
-
-def _csrc(name):
-    with open(os.path.join(ROOT, "oakink2-tamf_amd", "csrc", name)) as f:
-        return f.read()
-
-
-def _function_text(src, signature):
-    """the text of `src` from `signature` to the brace that closes the body that follows it"""
-    start = src.index(signature)
-    depth, i = 0, src.index("{", start)
-    while True:
-        depth += {"{": 1, "}": -1}.get(src[i], 0)
-        i += 1
-        if depth == 0:
-            return src[start:i]
 
 PAIRS = [(128, 256), (128, 384), (128, 512), (256, 1024), (512, 2048)]  # (d, ff): ARCH_TINY, ff = 3 d exactly, the test arch, arch_mdm / arch_refine, arch_mdm_l
 SIZES = [(1, 1), (1, 2), (2, 16), (3, 20), (3, 160), (7, 33), (31, 97), (32, 160), (64, 160), (64, 196), (64, 203)]  # (clips, frames), G: 5 prefix rows
@@ -36,25 +21,23 @@ def layouts(tmp_path_factory):
     """{(d, ff, eb, guard, B, T): dict of the layout's fields}, from one run of the stand-alone program"""
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     assert cxx, "no host C++ compiler"
-    hdr = _csrc("tamf_launch.h")
     main = r"""
 #include <cstdio>
-%s;
-%s
+#include "tamf_shapes.h"
 int main() {
   int d, ff, eb, guard, B, T;
-  while (scanf("%%d %%d %%d %%d %%d %%d", &d, &ff, &eb, &guard, &B, &T) == 6) {
+  while (scanf("%d %d %d %d %d %d", &d, &ff, &eb, &guard, &B, &T) == 6) {
     const long long Sp = (T + 5 + 7) / 8 * 8;
     const ScratchLayout s = scratch_layout(B * Sp, (long long)B * T, d, ff, eb, guard);
-    printf("%%d %%d %%d %%d %%d %%d : %%d %%llu %%llu %%llu %%llu %%llu %%llu %%llu %%llu\n", d, ff, eb, guard, B, T, (int)s.alias, s.host_bytes,
+    printf("%d %d %d %d %d %d : %d %llu %llu %llu %llu %llu %llu %llu %llu\n", d, ff, eb, guard, B, T, (int)s.alias, s.host_bytes,
            s.qk_off, s.a_off, s.h1_off, s.qk_bytes, s.a_bytes, s.h1_bytes, s.hidden_bytes);
   }
   return 0;
 }
-""" % (_function_text(hdr, "struct ScratchLayout"), _function_text(hdr, "static inline ScratchLayout scratch_layout("))
+"""
     tmp = tmp_path_factory.mktemp("layout")
     (tmp / "m.cpp").write_text(main)
-    subprocess.run([cxx, "-std=c++17", "-O0", "-Wall", "-o", str(tmp / "m"), str(tmp / "m.cpp")], check=True)
+    subprocess.run([cxx, "-std=c++17", "-O0", "-Wall", "-I", os.path.join(ROOT, "oakink2-tamf_amd", "csrc"), "-o", str(tmp / "m"), str(tmp / "m.cpp")], check=True)
     cases = [(d, ff, eb, g, B, T) for d, ff in PAIRS for eb in (2, 4) for g in (0, 256) for B, T in SIZES]
     out = subprocess.run([str(tmp / "m")], input="".join("%d %d %d %d %d %d\n" % c for c in cases), check=True, capture_output=True, text=True).stdout
     res = {}
