@@ -9,6 +9,7 @@ that description:
   POINTENC csrc/tamf_pointenc.hip -> libtamf_pointenc.so (include/tamf_pointenc.h: the PointBERT point encoder behind obj_embedding)
   TEXTENC  csrc/tamf_textenc.hip -> libtamf_textenc.so (include/tamf_textenc.h: the CLIP text tower behind text_embedding)
   ENCTRAIN csrc/tamf_enctrain.hip -> libtamf_enctrain.so (include/tamf_enctrain.h: the SegmentEncoder training step - forward, loss, gradients)
+  CONTACT  csrc/tamf_contact.hip -> libtamf_contact.so (include/tamf_contact.h: the contact-distance kernels of the training losses)
 POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
 score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
 Every library has its own sources, stamp and lock: building or loading one never touches another."""
@@ -33,6 +34,7 @@ MANO_LIB_PATH = os.path.join(LIB_DIR, "libtamf_mano.so")
 POINTENC_LIB_PATH = os.path.join(LIB_DIR, "libtamf_pointenc.so")
 TEXTENC_LIB_PATH = os.path.join(LIB_DIR, "libtamf_textenc.so")
 ENCTRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_enctrain.so")
+CONTACT_LIB_PATH = os.path.join(LIB_DIR, "libtamf_contact.so")
 
 EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_ctx_create", "tamf_ctx_resize", "tamf_ctx_destroy", "tamf_last_error", "tamf_load_weight", "tamf_finalize_weights",
@@ -64,6 +66,9 @@ TEXTENC_EXPORTS = [  # include/tamf_textenc.h: what libtamf_textenc.so exports
 ENCTRAIN_EXPORTS = [  # include/tamf_enctrain.h: what libtamf_enctrain.so exports
     "tamf_enctrain_last_error", "tamf_enctrain_create", "tamf_enctrain_destroy", "tamf_enctrain_bind", "tamf_enctrain_step",
     "tamf_enctrain_dropout_mask",
+]
+CONTACT_EXPORTS = [  # include/tamf_contact.h: what libtamf_contact.so exports
+    "tamf_contact_last_error", "tamf_contact_forward", "tamf_contact_backward",
 ]
 
 
@@ -265,10 +270,13 @@ TEXTENC = Library("libtamf_textenc", "tamf_textenc.hip", ("tamf_textenc.h", "tam
 ENCTRAIN = Library("libtamf_enctrain", "tamf_enctrain.hip", ("tamf_enctrain.h", "tamf_hip.h"),  # (tamf_hip.h for tamf_status and tamf_arch)
                    (Output("libtamf_enctrain.so", (), ENCTRAIN_EXPORTS),),
                    kernels=("_Z10lin_kernel", "_Z12wgrad_kernel", "_Z15attn_fwd_kernel", "_Z17attn_bwd_q_kernel", "_Z18attn_bwd_kv_kernel"))
+CONTACT = Library("libtamf_contact", "tamf_contact.hip", ("tamf_contact.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
+                  (Output("libtamf_contact.so", (), CONTACT_EXPORTS),),
+                  kernels=("_Z18contact_h2o_kernel", "_Z18contact_o2h_kernel", "_Z23contact_backward_kernel"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)
-TRAINING = (ENCTRAIN,)  # the SegmentEncoder training step (launch/train_encoder.py)
+TRAINING = (ENCTRAIN, CONTACT)  # the SegmentEncoder training step (launch/train_encoder.py); the contact-distance losses (contact.py)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -335,6 +343,11 @@ def load_textenc() -> ctypes.CDLL:
 def load_enctrain() -> ctypes.CDLL:
     """libtamf_enctrain.so (include/tamf_enctrain.h).  Independent of the other libraries."""
     return _load(ENCTRAIN, "libtamf_enctrain.so")
+
+
+def load_contact() -> ctypes.CDLL:
+    """libtamf_contact.so (include/tamf_contact.h).  Independent of the other libraries."""
+    return _load(CONTACT, "libtamf_contact.so")
 
 
 def load_from(path: str) -> ctypes.CDLL:

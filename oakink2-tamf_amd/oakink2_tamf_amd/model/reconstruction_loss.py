@@ -11,8 +11,10 @@ Every loss term is reduced in float64 and returned as a float64 scalar, whatever
 dtype): a float32 sum over up to T * E * 3 values would add its own rounding to the layer's.  The gradients that reach the model output
 are in its dtype.
 
-Not built: the contact-distance terms `dist_h` / `dist_o`.  They need the backward of the signed nearest-neighbour distance and of the
-vertex normals, which this package does not have; a positive coefficient raises NotImplementedError."""
+Not here: the contact-distance terms `dist_h` / `dist_o`; this class refuses a positive coefficient for them with
+NotImplementedError.  They are model/interaction_loss.HandInteractionLoss, a subclass, on the nearest-neighbour kernels of contact.py.
+(They need the backward of the signed nearest-neighbour distance with respect to the hand vertices only, not one of the vertex normals
+as the refusal's message still says: the normals enter through a sign, which has a zero derivative.)"""
 from __future__ import annotations
 
 import torch
@@ -122,17 +124,16 @@ class HandReconstructionLoss(torch.nn.Module):
             edge_len = coef * ((e_pred - e_gt).abs().to(f64) * mask[:, :, None, None]).mean(dim=(-3, -2, -1))
         return rec_joint, rec_vert, edge_len
 
-    def forward(self, model_output, batch):
-        """model_output (B, 99, 1, T): the generator's predicted pose representation; batch: `hand_side` (B strings "rh" / "lh"),
-        `shape` (B, T, 10), `mask` (B, T), `pose_repr` (B, T, 99) the ground truth.  -> (loss, loss_dict) with the reference's keys;
-        every term is summed over the clips, as in the reference, and is a float64 scalar (see _terms)."""
+    def _per_side(self, model_output, batch):
+        """The decode + MANO calls of `forward`, per hand side present in the batch: yields (layer, idx, verts_pred, joints_pred, verts_gt,
+        joints_gt, mask[idx]) with idx the side's clips (a LongTensor) and (nb, T, V | 21, 3) tensors in the model output's dtype.  One
+        differentiable layer call per side over all of its predicted frames, one inference call for their ground truth."""
         B, T = model_output.shape[0], model_output.shape[3]
         pred = model_output.squeeze(2).permute(0, 2, 1)  # (B, T, 99)
         gt, shape, mask, sides = batch["pose_repr"], batch["shape"], batch["mask"], list(batch["hand_side"])
         if len(sides) != B or any(s not in self.layers for s in sides):
             raise ValueError(f"unexpected hand_side: {sides}")
         mask = mask.to(pred.dtype)
-        total = {"rec_joint": 0.0, "rec_vert": 0.0, "edge_len": 0.0}
         for side, layer in self.layers.items():
             rows = [i for i, s in enumerate(sides) if s == side]
             if not rows:
@@ -150,7 +151,15 @@ class HandReconstructionLoss(torch.nn.Module):
             joints_p = out.joints.reshape(nb, T, -1, 3).to(pred.dtype) + tsl_p.unsqueeze(2)
             verts_g = out_g.verts.reshape(nb, T, -1, 3).to(pred.dtype) + tsl_g.unsqueeze(2)
             joints_g = out_g.joints.reshape(nb, T, -1, 3).to(pred.dtype) + tsl_g.unsqueeze(2)
-            for key, term in zip(("rec_joint", "rec_vert", "edge_len"), self._terms(verts_p, joints_p, verts_g, joints_g, mask[idx], True)):
+            yield layer, idx, verts_p, joints_p, verts_g, joints_g, mask[idx]
+
+    def forward(self, model_output, batch):
+        """model_output (B, 99, 1, T): the generator's predicted pose representation; batch: `hand_side` (B strings "rh" / "lh"),
+        `shape` (B, T, 10), `mask` (B, T), `pose_repr` (B, T, 99) the ground truth.  -> (loss, loss_dict) with the reference's keys;
+        every term is summed over the clips, as in the reference, and is a float64 scalar (see _terms)."""
+        total = {"rec_joint": 0.0, "rec_vert": 0.0, "edge_len": 0.0}
+        for _, _, verts_p, joints_p, verts_g, joints_g, mask in self._per_side(model_output, batch):
+            for key, term in zip(("rec_joint", "rec_vert", "edge_len"), self._terms(verts_p, joints_p, verts_g, joints_g, mask, True)):
                 if torch.is_tensor(term):
                     total[key] = total[key] + term.sum()
         loss = (self.coef_rec_joint_loss * total["rec_joint"] + self.coef_rec_vert_loss * total["rec_vert"]
