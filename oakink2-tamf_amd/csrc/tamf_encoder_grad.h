@@ -17,45 +17,11 @@
 //   site 3 + 4 l         GELU output              element = row * ff + col
 //   site 4 + 4 l         linear2 output           element = row * 64 + col
 #pragma once
+#include "tamf_dropout.h"
 #include "tamf_encoder.h"
 
 constexpr int EG_H = ENC_D / ENC_HD;  // heads
 constexpr int EG_MAX_S = 512;         // token rows of a clip: K_h | V_h (or Q_h | dO_h) of one head in 64 KiB of LDS
-
-// rows of a (clips x rows-per-clip) selection inside a [B][S][ld] buffer: row m lives at (m / G) * gs + (m % G) * ld floats
-struct RowMap {
-  int G;
-  long gs, ld;
-  TAMF_DEV long at(int m) const { return (long)(m / G) * gs + (long)(m % G) * ld; }
-};
-
-struct Drop {
-  uint32_t k0, k1, step, thr;  // key, step, keep threshold (keep when the draw >= thr)
-  float scale;                 // 1 / (1 - p)
-  const long long* clip;       // [B] clip ids or null (b)
-};
-TAMF_DEV uint32_t drop_key0(const Drop& d, int site) { return d.k0 ^ ((uint32_t)site * 0x9E3779B1u); }
-TAMF_DEV bool drop_keep_id(const Drop& d, int site, unsigned long long c, uint32_t e) {
-  if (d.thr == 0) return true;
-  uint32_t r[4];
-  philox4x32_10(e >> 2, d.step, (uint32_t)(c & 0xFFFFFFFFu), (uint32_t)(c >> 32), drop_key0(d, site), d.k1, r);
-  const uint32_t v = (e & 3) == 0 ? r[0] : (e & 3) == 1 ? r[1] : (e & 3) == 2 ? r[2] : r[3];
-  return v >= d.thr;
-}
-TAMF_DEV bool drop_keep(const Drop& d, int site, int b, uint32_t e) {
-  if (d.thr == 0) return true;
-  return drop_keep_id(d, site, d.clip ? (unsigned long long)d.clip[b] : (unsigned long long)b, e);
-}
-// the factor of a dropped-out value: 0 or 1 / (1 - p)
-TAMF_DEV float drop_factor(const Drop& d, int site, int b, uint32_t e) { return drop_keep(d, site, b, e) ? d.scale : 0.f; }
-
-TAMF_DEV float silu_grad(float x) {
-  const float s = 1.0f / (1.0f + expf(-x));
-  return s * (1.0f + x * (1.0f - s));
-}
-TAMF_DEV float gelu_grad(float x) {
-  return 0.5f * (1.0f + erff(x * 0.70710678118654752440f)) + x * 0.3989422804014327f * expf(-0.5f * x * x);
-}
 
 enum EgMode {
   EG_LIN = 0,        // C = v
@@ -163,16 +129,6 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
     const int nn = n0 + 4 * g + i;
     if (nn < a.N) a.part[((long)s * a.N + nn) * K1 + k] = acc[i];
   }
-}
-// dW[n][k] (k < K) and db[n] (k = K, K1 = K + 1) = the partial sums added in split order; K1 = K: no bias column
-__global__ void reduce_kernel(const float* part, int nsplit, int N, int K1, int K, float* dW, float* db) {
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x, tot = (long)N * K1;
-  if (e >= tot) return;
-  float s = 0.f;
-  for (int i = 0; i < nsplit; ++i) s += part[(long)i * tot + e];
-  const int n = (int)(e / K1), k = (int)(e % K1);
-  if (k < K) dW[(long)n * K + k] = s;
-  else db[n] = s;
 }
 // part[s][c] = sum over the rows of split s of X[xm(r) + c], c < 64 (LayerNorm gain / bias gradients); block = 64 threads
 __global__ void colsum_kernel(const float* X, RowMap xm, int R, int chunk, float* part) {
@@ -433,9 +389,4 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* act, const long lo
     for (int b = 0; b < B; ++b) s += lb[b];
     *loss = s / (float)B;
   }
-}
-
-__global__ void dropout_mask_kernel(Drop d, int site, unsigned long long clip, long n, unsigned char* out) {
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) out[e] = drop_keep_id(d, site, clip, (uint32_t)e) ? 1 : 0;
 }

@@ -170,18 +170,7 @@ void declare_model(tamf_enctrain_ctx* c) {
   c->p4 = declare_linear(c, "output_process.poseFinal.4", a.input_dim, D);
 }
 
-Drop make_drop(uint64_t seed, uint32_t step, float p, const long long* clip) {
-  Drop d;
-  d.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  d.k1 = (uint32_t)(seed >> 32);
-  d.step = step;
-  d.thr = (uint32_t)std::min(4294967295.0, std::floor((double)p * 4294967296.0));
-  d.scale = 1.0f / (1.0f - p);
-  d.clip = clip;
-  return d;
-}
-
-RowMap flat(long ld) { return RowMap{1 << 30, 0, ld}; }
+RowMap flat(long ld) { return RowMap{ROWMAP_FLAT, 0, ld}; }
 
 // the epilogue of a lin_kernel launch: an EgMode with the operands that mode reads
 struct Epi {

@@ -1,0 +1,616 @@
+// libtamf_refinetrain.so (include/tamf_refinetrain.h): the host side of the SegmentRefineModel training step - the table of bound
+// tensors, the workspace and the launch sequences of the kernels of tamf_trunk_grad.h.  Host conventions of tamf_weights.h: an int
+// status, a thread-local last-error string, nothing thrown across the ABI.
+//
+// The layer stack (forward_layer / backward_layer) sees token rows [B][S][d] and nothing of the model around it; the refiner is its
+// input stage (3 prefix rows, frames merged from pose | object trajectory | hand->object distance) and its head (x_in + poseFinal).
+//
+// Row counts of the workspace structs below: R = B (T + 3) token rows, BT = B T frame rows; the context carves them for (max_batch,
+// max_frames), a call addresses them with its own B and T.
+#include "tamf_weights.h"
+
+#include <tuple>
+
+#include "../../include/tamf_refinetrain.h"
+#include "tamf_trunk_grad.h"
+
+namespace {
+
+constexpr int MAX_SPLIT = 64, SPLIT_ROWS = 256, PREFIX = 3, MAX_S = 1024;
+
+struct Bound {
+  std::vector<int64_t> shape;
+  bool trainable = true;
+  const float* p = nullptr;
+  float* g = nullptr;
+};
+// one declared (weight, bias) pair, N x K and N, where it is bound - a linear map, or the gain and bias of a LayerNorm (K = 0)
+struct Lin {
+  const Bound *w = nullptr, *b = nullptr;
+  int N = 0, K = 0;
+};
+struct LayerP {
+  Lin inproj, out, l1, l2, n1, n2;
+};
+
+struct Dims {
+  long B, BT, R;
+  int D, H, F, ff, sd, od, qd, hd;
+};
+Dims dims(const tamf_arch& a, long B, long T) {
+  return {B, B * T, B * (T + PREFIX), a.latent_dim, a.num_heads, a.input_dim, a.ff_size, a.hand_shape_dim, a.obj_embed_dim, a.obj_input_dim, a.h2o_dim};
+}
+
+// ---- the workspace (offsets in floats): what the forward keeps for the backward, then the backward's own buffers ----
+struct InputWs {
+  long shm, oem, trm, cat, zpre, z, pre;
+};
+InputWs carve_input(Carver& cv, const Dims& n) {
+  InputWs x;
+  x.shm = cv.take(n.B * n.sd);            // [B][sd]     the hand shape, mean over the frames
+  x.oem = cv.take(n.B * n.od);            // [B][od]     the object embedding, mean over the objects
+  x.trm = cv.take(n.BT * n.qd);           // [BT][qd]    the object trajectory, mean over the objects
+  x.cat = cv.take(n.BT * 3 * n.D);        // [BT][3 d]   pose | trajectory | distance embeddings
+  x.zpre = cv.take(n.BT * n.D);           // [BT][d]     the first merge map before ...
+  x.z = cv.take(n.BT * n.D);              //             ... and after SiLU
+  x.pre = cv.take(n.R * n.D);             // [R][d]      token rows before nan_to_num and PE
+  return x;
+}
+struct LayerWs {
+  long x, qkv, stat, att, x1pre, x1, x2pre, hpre, gel;
+};
+LayerWs carve_layer(Carver& cv, const Dims& n) {
+  LayerWs x;
+  x.x = cv.take(n.R * n.D);               // [R][d]        the layer's input
+  x.qkv = cv.take(n.R * 3 * n.D);         // [R][3 d]
+  x.stat = cv.take(n.R * n.H * 2);        // [B][H][S][2]  softmax (max, sum)
+  x.att = cv.take(n.R * n.D);             // [R][d]        attention output
+  x.x1pre = cv.take(n.R * n.D);           // [R][d]        LayerNorm 1: input,
+  x.x1 = cv.take(n.R * n.D);              //               output
+  x.x2pre = cv.take(n.R * n.D);           // [R][d]        LayerNorm 2: input (its output is the next layer's x)
+  x.hpre = cv.take(n.R * n.ff);           // [R][ff]       the feed-forward hidden rows before GELU,
+  x.gel = cv.take(n.R * n.ff);            //               after GELU and dropout
+  return x;
+}
+struct HeadWs {
+  long xlast, outpre;
+};
+HeadWs carve_head(Carver& cv, const Dims& n) {
+  HeadWs x;
+  x.xlast = cv.take(n.R * n.D);           // [R][d]   the last layer's output
+  x.outpre = cv.take(n.BT * n.F);         // [BT][F]  x_in + poseFinal(...) before nan_to_num
+  return x;
+}
+struct GradWs {
+  long dx, dz, dym, tt, dx1, datt, dqkv, dh, delta, dpre, dzin, dcat, dout, slab;
+};
+GradWs carve_grads(Carver& cv, const Dims& n, long slab_nk) {
+  GradWs x;
+  x.dx = cv.take(n.R * n.D);              // [R][d] each: the gradient of a layer's output / input,
+  x.dz = cv.take(n.R * n.D);              //   of a LayerNorm's input,
+  x.dym = cv.take(n.R * n.D);             //   of the linear output under that LayerNorm's residual dropout,
+  x.tt = cv.take(n.R * n.D);              //   dy * xhat (the gain gradient before the column sum),
+  x.dx1 = cv.take(n.R * n.D);             //   of LayerNorm 1's output,
+  x.datt = cv.take(n.R * n.D);            //   of the attention output
+  x.dqkv = cv.take(n.R * 3 * n.D);        // [R][3 d]
+  x.dh = cv.take(n.R * n.ff);             // [R][ff]
+  x.delta = cv.take(n.R * n.H);           // [B][H][S]  sum_k P dP of every query
+  x.dpre = cv.take(n.R * n.D);            // [R][d]     of InputWs::pre,
+  x.dzin = cv.take(n.BT * n.D);           // [BT][d]    zpre,
+  x.dcat = cv.take(n.BT * 3 * n.D);       // [BT][3 d]  cat
+  x.dout = cv.take(n.BT * n.F);           // [BT][F]    of HeadWs::outpre
+  x.slab = cv.take(slab_nk * MAX_SPLIT);  // [<= 64 splits][N][K + 1] weight-gradient partial sums of the largest linear map
+  return x;
+}
+
+// the caller's tensors of one forward (device memory; cnt is the context's copy of obj_num or null)
+struct Batch {
+  const float *pose, *dist, *shape, *oemb, *traj;
+  const uint8_t* side;
+  const int* cnt;
+  float* out;
+  int nobj;
+};
+
+}  // namespace
+
+struct tamf_refinetrain_ctx {
+  tamf_arch arch;
+  int maxB, maxT, device;
+  std::map<std::string, Bound> t;                                      // (nodes are address-stable: Lin points into them)
+  std::vector<const std::pair<const std::string, Bound>*> order;       // in declaration order
+  long slab_nk = 0;                                                    // the largest N (K + 1) of a declared linear map
+  const Bound *rh, *lh, *pe;
+  Lin shape, obj, pose, traj, dist, m0, m2, head;
+  std::vector<LayerP> lp;
+  float* ws = nullptr;
+  int* cnt = nullptr;         // [maxB]
+  long long* clip = nullptr;  // [maxB]
+  InputWs in;
+  std::vector<LayerWs> lw;
+  HeadWs hw;
+  GradWs g;
+  // the forward whose activations the workspace holds
+  bool have_forward = false;
+  int B = 0, T = 0;
+  // tamf_refinetrain_set_profile: a pair of events around every launch, read and freed by tamf_refinetrain_get_profile
+  bool profile = false;
+  std::vector<std::tuple<const char*, hipEvent_t, hipEvent_t>> marks;
+  Batch io{};
+  Drop drop{};
+};
+
+namespace {
+
+const Bound* declare(tamf_refinetrain_ctx* c, const std::string& k, std::vector<int64_t> shape, bool trainable = true) {
+  auto it = c->t.emplace(k, Bound{std::move(shape), trainable}).first;
+  c->order.push_back(&*it);
+  return &it->second;
+}
+Lin declare_pair(tamf_refinetrain_ctx* c, const std::string& wk, const std::string& bk, int o, int i) {
+  c->slab_nk = std::max(c->slab_nk, (long)o * (i + 1));
+  const Bound* w = declare(c, wk, {o, i});
+  return Lin{w, declare(c, bk, {o}), o, i};
+}
+Lin declare_linear(tamf_refinetrain_ctx* c, const std::string& k, int o, int i) { return declare_pair(c, k + ".weight", k + ".bias", o, i); }
+Lin declare_norm(tamf_refinetrain_ctx* c, const std::string& k, int D) {
+  const Bound* w = declare(c, k + ".weight", {D});
+  return Lin{w, declare(c, k + ".bias", {D}), D, 0};
+}
+// every tensor of the state dict, in its order
+void declare_model(tamf_refinetrain_ctx* c) {
+  const tamf_arch& a = c->arch;
+  const int D = a.latent_dim;
+  c->rh = declare(c, "hand_side_process.rh_embed", {D}, false);
+  c->lh = declare(c, "hand_side_process.lh_embed", {D}, false);
+  c->shape = declare_linear(c, "hand_shape_process.shape_embed", D, a.hand_shape_dim);
+  c->obj = declare_linear(c, "obj_embed_process.embedding", D, a.obj_embed_dim);
+  c->pose = declare_linear(c, "input_process.poseEmbedding", D, a.input_dim);
+  c->traj = declare_linear(c, "obj_input_process.poseEmbedding", D, a.obj_input_dim);
+  c->dist = declare_linear(c, "h2o_dist_input_process.poseEmbedding", D, a.h2o_dim);
+  c->m0 = declare_linear(c, "input_merge.0", D, 3 * D);
+  c->m2 = declare_linear(c, "input_merge.2", D, D);
+  c->pe = declare(c, "sequence_pos_encoder.pe", {5000, 1, D}, false);
+  c->lp.resize(a.num_layers);
+  for (int l = 0; l < a.num_layers; ++l) {
+    const std::string p = "seqTransEncoder.layers." + std::to_string(l) + ".";
+    LayerP& x = c->lp[l];
+    x.inproj = declare_pair(c, p + "self_attn.in_proj_weight", p + "self_attn.in_proj_bias", 3 * D, D);
+    x.out = declare_linear(c, p + "self_attn.out_proj", D, D);
+    x.l1 = declare_linear(c, p + "linear1", a.ff_size, D);
+    x.l2 = declare_linear(c, p + "linear2", D, a.ff_size);
+    x.n1 = declare_norm(c, p + "norm1", D);
+    x.n2 = declare_norm(c, p + "norm2", D);
+  }
+  c->head = declare_linear(c, "output_process.poseFinal", a.input_dim, D);
+}
+
+RowMap flat(long ld) { return RowMap{ROWMAP_FLAT, 0, ld}; }
+
+// the epilogue of a tg_lin_kernel launch: a TgMode with the operands that mode reads
+struct Epi {
+  int mode = TG_LIN;
+  float* C2 = nullptr;
+  const float* R = nullptr;
+  int site = 0;
+};
+Epi silu(float* pre) { return {TG_SILU, pre}; }
+Epi gelu_drop(float* pre, int site) { return {TG_GELU_DROP, pre, nullptr, site}; }
+Epi drop_res(const float* res, int site) { return {TG_DROP_RES, nullptr, res, site}; }
+Epi bwd_silu(const float* pre) { return {TG_BWD_SILU, nullptr, pre}; }
+Epi bwd_gelu_drop(const float* pre, int site) { return {TG_BWD_GELU_DROP, nullptr, pre, site}; }
+Epi bwd_res(const float* res) { return {TG_BWD_RES, nullptr, res}; }
+
+// ---- the input stage: means, the hand-side row, x0 = drop(nan_to_num(pre) + PE), the output mask ----
+struct PrepArgs {
+  const float *shape, *oemb, *traj;  // (B,T,sd) (B,nobj,od) (B,nobj,T,qd)
+  const unsigned char* side;         // [B] 0 = rh, 1 = lh
+  const int* cnt;                    // [B] or null
+  const float *rh, *lh;              // [d] each
+  float *shm, *oem, *trm, *pre;      // [B][sd] [B][od] [B*T][qd]; pre [B][S][d]: row 0 is written here
+  int B, T, D, nobj, sd, od, qd;
+};
+__global__ void prep_kernel(const PrepArgs a) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int S = a.T + PREFIX;
+  const long n0 = (long)a.B * a.sd, n1 = n0 + (long)a.B * a.od, n2 = n1 + (long)a.B * a.T * a.qd, n3 = n2 + (long)a.B * a.D;
+  if (e < n0) {
+    const int b = (int)(e / a.sd), c = (int)(e % a.sd);
+    double s = 0.0;  // (T terms of one sign: a float32 running sum would lose log2(T) bits of the hand-shape row)
+    for (int t = 0; t < a.T; ++t) s += (double)a.shape[((long)b * a.T + t) * a.sd + c];
+    a.shm[e] = (float)(s / (double)a.T);
+  } else if (e < n1) {
+    const long i = e - n0;
+    const int b = (int)(i / a.od), c = (int)(i % a.od);
+    const int n = a.cnt ? max(1, min(a.cnt[b], a.nobj)) : a.nobj;
+    float s = 0.f;
+    for (int o = 0; o < n; ++o) s += a.oemb[((long)b * a.nobj + o) * a.od + c];
+    a.oem[i] = s / (float)n;
+  } else if (e < n2) {
+    const long i = e - n1;
+    const int c = (int)(i % a.qd);
+    const long bt = i / a.qd;
+    const int b = (int)(bt / a.T), t = (int)(bt % a.T);
+    const int n = a.cnt ? max(1, min(a.cnt[b], a.nobj)) : a.nobj;
+    float s = 0.f;
+    for (int o = 0; o < n; ++o) s += a.traj[(((long)b * a.nobj + o) * a.T + t) * a.qd + c];
+    a.trm[i] = s / (float)n;
+  } else if (e < n3) {
+    const long i = e - n2;
+    const int b = (int)(i / a.D), c = (int)(i % a.D);
+    a.pre[(long)b * S * a.D + c] = (a.side[b] ? a.lh : a.rh)[c];
+  }
+}
+// X0 = drop(nan_to_num(pre) + PE) over [B][S][d]; its backward: dpre = dX0 * drop factor * isfinite(pre)
+__global__ void assemble_kernel(const float* pre, const float* pe, float* x0, const float* dx0, float* dpre, int B, int S, int D, Drop d) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)B * S * D) return;
+  const int b = (int)(e / ((long)S * D));
+  const uint32_t el = (uint32_t)(e % ((long)S * D));
+  const float f = drop_factor(d, 0, b, el), v = pre[e];
+  if (x0) x0[e] = (nan_to_num(v) + pe[el]) * f;
+  else dpre[e] = (v - v == 0.f) ? dx0[e] * f : 0.f;  // (v - v: 0 for a finite v, NaN otherwise)
+}
+// dpre = isfinite(pre) ? dout : 0 (the output's nan_to_num)
+__global__ void finite_mask_kernel(const float* pre, const float* dout, float* dpre, long n) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  const float v = pre[e];
+  dpre[e] = (v - v == 0.f) ? dout[e] : 0.f;
+}
+
+struct Step {
+  tamf_refinetrain_ctx* c = nullptr;
+  hipStream_t st = nullptr;
+  Dims n{};
+  int B = 0, T = 0, S = 0, D = 0;
+  Batch io{};
+  Drop drop{};
+  hipError_t err = hipSuccess;
+  const char* tag = "other";  // what the next launches are called in the profile
+
+  float* w(long off) const { return c->ws + off; }
+  float* xof(int l) const { return w(l < (int)c->lw.size() ? c->lw[l].x : c->hw.xlast); }  // layer l's input; xof(L): the output
+  RowMap rows(int nq, long ld) const { return RowMap{nq, (long)S * ld, ld}; }  // nq rows of every clip inside [B][S][ld]
+  RowMap tok(long ld) const { return rows(S, ld); }                            // every token row, split into (clip, row)
+  RowMap one() const { return rows(1, D); }
+  RowMap frames() const { return rows(T, D); }
+
+  // every launch of the library: the first launch error is kept
+  template <class K, class... A>
+  void launch(K kernel, dim3 grid, int block, size_t lds, A... args) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const bool timed = c && c->profile && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    if (timed) (void)hipEventRecord(e0, st);
+    kernel<<<grid, block, lds, st>>>(args...);
+    if (err == hipSuccess) err = hipGetLastError();
+    if (timed) {
+      (void)hipEventRecord(e1, st);
+      c->marks.emplace_back(tag, e0, e1);
+    }
+  }
+  int status() const { return err == hipSuccess ? 0 : fail(TAMF_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(err)); }
+
+  void lin(TgLin a, const Epi& e, bool wt) {
+    a.rm = a.cm;
+    a.mode = e.mode;
+    a.C2 = e.C2;
+    a.R = e.R;
+    a.site = e.site;
+    a.d = drop;
+    const dim3 grid((a.M + TG_T - 1) / TG_T, (a.N + TG_T - 1) / TG_T);
+    tag = wt ? "tg_lin_kernel<dgrad>" : "tg_lin_kernel<fwd>";
+    if (wt) launch(tg_lin_kernel<true>, grid, 256, 0, a);
+    else launch(tg_lin_kernel<false>, grid, 256, 0, a);
+  }
+  // C (M, N) = epilogue(A (M, K) . W^T + b) of a linear map
+  void fwd(const Lin& l, const float* A, RowMap am, float* C, RowMap cm, int M, const Epi& e = {}) {
+    TgLin a{};
+    a.A = A, a.am = am, a.W = l.w->p, a.swn = l.K, a.swk = 1, a.bias = l.b->p, a.C = C, a.cm = cm, a.M = M, a.N = l.N, a.K = l.K;
+    lin(a, e, false);
+  }
+  // the data gradient of the same map: dA (M, K) = epilogue(dY (M, N) . W)
+  void dgrad(const Lin& l, const float* dY, RowMap ym, float* dA, RowMap cm, int M, const Epi& e = {}) {
+    TgLin a{};
+    a.A = dY, a.am = ym, a.W = l.w->p, a.swn = 1, a.swk = l.K, a.C = dA, a.cm = cm, a.M = M, a.N = l.K, a.K = l.N;
+    lin(a, e, true);
+  }
+  // the split of R rows: a function of the row count alone
+  static int splits(int R) { return std::max(1, std::min(MAX_SPLIT, (R + SPLIT_ROWS - 1) / SPLIT_ROWS)); }
+  // its weight and bias gradients from its output gradient Y and its input A over R rows
+  void wgrad(const Lin& l, const float* Y, RowMap ym, const float* A, RowMap am, int R) {
+    const int N = l.N, K = l.K, nsplit = splits(R), chunk = ((R + nsplit - 1) / nsplit + TG_K - 1) / TG_K * TG_K;
+    tag = "tg_wgrad_kernel";
+    launch(tg_wgrad_kernel, dim3((N + TG_T - 1) / TG_T, (K + 1 + TG_T - 1) / TG_T, nsplit), 256, 0, TgWgrad{Y, ym, A, am, w(c->g.slab), R, N, K, chunk});
+    tag = "reduce_kernel";
+    launch(reduce_kernel, blocks((long)N * (K + 1), 256), 256, 0, w(c->g.slab), nsplit, N, K + 1, K, l.w->g, l.b->g);
+  }
+  // the column sums of two [R][d] buffers at once (a LayerNorm's gain and bias gradients), through the two halves of the slab
+  void colsum2(const float* A, const float* Bm, int R, float* outa, float* outb) {
+    const int nsplit = splits(R);
+    float *pa = w(c->g.slab), *pb = pa + (long)MAX_SPLIT * D;
+    tag = "tg_colsum2_kernel + reduce";
+    launch(tg_colsum2_kernel, dim3(nsplit, D / 64), 256, 0, A, Bm, D, R, (R + nsplit - 1) / nsplit, pa, pb);
+    launch(reduce_kernel, blocks(D, 256), 256, 0, pa, nsplit, 1, D, D, outa, nullptr);
+    launch(reduce_kernel, blocks(D, 256), 256, 0, pb, nsplit, 1, D, D, outb, nullptr);
+  }
+  void ln_fwd(const float* X, float* Y, const Lin& norm) {
+    tag = "tg_ln_fwd_kernel";
+    launch(tg_ln_fwd_kernel, blocks(n.R, 4), 256, 0, X, Y, norm.w->p, norm.b->p, (int)n.R, D);
+  }
+  // LayerNorm backward of dy (offsets): dz, dym = dz under the dropout of `site`, the gain and bias gradients
+  void ln_bwd(long dy, long pre, const Lin& norm, int site) {
+    const GradWs& g = c->g;
+    tag = "tg_ln_bwd_kernel";
+    launch(tg_ln_bwd_kernel, blocks(n.R, 4), 256, 0, w(dy), w(pre), norm.w->p, w(g.dz), w(g.dym), w(g.tt), (int)n.R, D, S, site, drop);
+    colsum2(w(g.tt), w(dy), (int)n.R, norm.w->g, norm.b->g);
+  }
+  dim3 attn_grid() const { return dim3((S + 15) / 16, n.H, B); }
+
+  // ---- the layer stack: token rows in, token rows out ----
+  void forward_layer(int l) {
+    const LayerWs& x = c->lw[l];
+    const LayerP& p = c->lp[l];
+    const int site = 1 + 4 * l, R = (int)n.R;
+    fwd(p.inproj, xof(l), flat(D), w(x.qkv), flat(3 * D), R);
+    tag = "tg_attn_fwd_kernel";
+    launch(tg_attn_fwd_kernel, attn_grid(), 64, 0, TgAttn{w(x.qkv), w(x.att), w(x.stat), nullptr, nullptr, nullptr, S, n.H, site, drop});
+    fwd(p.out, w(x.att), flat(D), w(x.x1pre), tok(D), R, drop_res(xof(l), site + 1));
+    ln_fwd(w(x.x1pre), w(x.x1), p.n1);
+    fwd(p.l1, w(x.x1), flat(D), w(x.gel), tok(n.ff), R, gelu_drop(w(x.hpre), site + 2));
+    fwd(p.l2, w(x.gel), flat(n.ff), w(x.x2pre), tok(D), R, drop_res(w(x.x1), site + 3));
+    ln_fwd(w(x.x2pre), xof(l + 1), p.n2);
+  }
+  // g.dx: the gradient of the layer's output on entry, of its input on return
+  void backward_layer(int l) {
+    const LayerWs& x = c->lw[l];
+    const LayerP& p = c->lp[l];
+    const GradWs& g = c->g;
+    const int site = 1 + 4 * l, R = (int)n.R;
+    // LayerNorm 2, the feed-forward block
+    ln_bwd(g.dx, x.x2pre, p.n2, site + 3);
+    wgrad(p.l2, w(g.dym), flat(D), w(x.gel), flat(n.ff), R);
+    dgrad(p.l2, w(g.dym), flat(D), w(g.dh), tok(n.ff), R, bwd_gelu_drop(w(x.hpre), site + 2));
+    wgrad(p.l1, w(g.dh), flat(n.ff), w(x.x1), flat(D), R);
+    dgrad(p.l1, w(g.dh), flat(n.ff), w(g.dx1), flat(D), R, bwd_res(w(g.dz)));
+    // LayerNorm 1, out-projection, attention, in-projection
+    ln_bwd(g.dx1, x.x1pre, p.n1, site + 1);
+    wgrad(p.out, w(g.dym), flat(D), w(x.att), flat(D), R);
+    dgrad(p.out, w(g.dym), flat(D), w(g.datt), flat(D), R);
+    const TgAttn a{w(x.qkv), w(x.att), w(x.stat), w(g.datt), w(g.dqkv), w(g.delta), S, n.H, site, drop};
+    tag = "tg_attn_bwd_q_kernel";
+    launch(tg_attn_bwd_q_kernel, attn_grid(), 64, 0, a);
+    tag = "tg_attn_bwd_kv_kernel";
+    launch(tg_attn_bwd_kv_kernel, attn_grid(), 64, 0, a);
+    wgrad(p.inproj, w(g.dqkv), flat(3 * D), xof(l), flat(D), R);
+    dgrad(p.inproj, w(g.dqkv), flat(3 * D), w(g.dx), flat(D), R, bwd_res(w(g.dz)));
+  }
+
+  // ---- the refiner around it ----
+  void forward_input() {
+    const InputWs& x = c->in;
+    const PrepArgs a{io.shape, io.oemb, io.traj, io.side, io.cnt, c->rh->p, c->lh->p, w(x.shm), w(x.oem), w(x.trm), w(x.pre),
+                     B, T, D, io.nobj, n.sd, n.od, n.qd};
+    tag = "input stage (elementwise)";
+    launch(prep_kernel, blocks(n.B * n.sd + n.B * n.od + n.BT * n.qd + n.B * D, 256), 256, 0, a);
+    fwd(c->shape, w(x.shm), flat(n.sd), w(x.pre) + 1 * D, one(), B);
+    fwd(c->obj, w(x.oem), flat(n.od), w(x.pre) + 2 * D, one(), B);
+    fwd(c->pose, io.pose, flat(n.F), w(x.cat), flat(3 * D), (int)n.BT);
+    fwd(c->traj, w(x.trm), flat(n.qd), w(x.cat) + D, flat(3 * D), (int)n.BT);
+    fwd(c->dist, io.dist, flat(n.hd), w(x.cat) + 2 * D, flat(3 * D), (int)n.BT);
+    fwd(c->m0, w(x.cat), flat(3 * D), w(x.z), flat(D), (int)n.BT, silu(w(x.zpre)));
+    fwd(c->m2, w(x.z), flat(D), w(x.pre) + PREFIX * D, frames(), (int)n.BT);
+    tag = "input stage (elementwise)";
+    launch(assemble_kernel, blocks(n.R * D, 256), 256, 0, w(x.pre), c->pe->p, xof(0), nullptr, nullptr, B, S, D, drop);
+  }
+  void forward_head() {
+    const float* fr = xof((int)c->lw.size()) + PREFIX * D;
+    Epi e{TG_HEAD_RES, w(c->hw.outpre), io.pose};
+    fwd(c->head, fr, frames(), io.out, flat(n.F), (int)n.BT, e);
+  }
+  void backward_head(const float* gout) {
+    const GradWs& g = c->g;
+    const float* fr = xof((int)c->lw.size()) + PREFIX * D;
+    tag = "input stage (elementwise)";
+    launch(finite_mask_kernel, blocks(n.BT * n.F, 256), 256, 0, w(c->hw.outpre), gout, w(g.dout), n.BT * n.F);
+    wgrad(c->head, w(g.dout), flat(n.F), fr, frames(), (int)n.BT);
+    if (err == hipSuccess) err = hipMemsetAsync(w(g.dx), 0, n.R * D * sizeof(float), st);  // (the prefix rows feed no output row)
+    dgrad(c->head, w(g.dout), flat(n.F), w(g.dx) + PREFIX * D, frames(), (int)n.BT);
+  }
+  void backward_input() {
+    const InputWs& x = c->in;
+    const GradWs& g = c->g;
+    tag = "input stage (elementwise)";
+    launch(assemble_kernel, blocks(n.R * D, 256), 256, 0, w(x.pre), c->pe->p, nullptr, w(g.dx), w(g.dpre), B, S, D, drop);
+    wgrad(c->shape, w(g.dpre) + 1 * D, one(), w(x.shm), flat(n.sd), B);
+    wgrad(c->obj, w(g.dpre) + 2 * D, one(), w(x.oem), flat(n.od), B);
+    const float* dfr = w(g.dpre) + PREFIX * D;
+    wgrad(c->m2, dfr, frames(), w(x.z), flat(D), (int)n.BT);
+    dgrad(c->m2, dfr, frames(), w(g.dzin), flat(D), (int)n.BT, bwd_silu(w(x.zpre)));
+    wgrad(c->m0, w(g.dzin), flat(D), w(x.cat), flat(3 * D), (int)n.BT);
+    dgrad(c->m0, w(g.dzin), flat(D), w(g.dcat), flat(3 * D), (int)n.BT);
+    wgrad(c->pose, w(g.dcat), flat(3 * D), io.pose, flat(n.F), (int)n.BT);
+    wgrad(c->traj, w(g.dcat) + D, flat(3 * D), w(x.trm), flat(n.qd), (int)n.BT);
+    wgrad(c->dist, w(g.dcat) + 2 * D, flat(3 * D), io.dist, flat(n.hd), (int)n.BT);
+  }
+};
+
+Step make_step(tamf_refinetrain_ctx* c, hipStream_t st) {
+  Step s;
+  s.c = c;
+  s.st = st;
+  s.n = dims(c->arch, c->B, c->T);
+  s.B = c->B, s.T = c->T, s.S = c->T + PREFIX, s.D = c->arch.latent_dim;
+  s.io = c->io;
+  s.drop = c->drop;
+  return s;
+}
+
+std::string range(const char* what, long v, long lo, long hi) {
+  return std::string(what) + " = " + std::to_string(v) + " outside [" + std::to_string(lo) + ", " + std::to_string(hi) + "]";
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* tamf_refinetrain_last_error(void) { return g_error.c_str(); }
+
+int tamf_refinetrain_create(const tamf_arch* arch, int32_t max_batch, int32_t max_frames, int32_t device, tamf_refinetrain_ctx** out) {
+  if (!arch || !out) return fail(TAMF_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (arch->num_heads < 1 || arch->num_heads > TG_MAXC) return fail(TAMF_ERR_INVALID, range("num_heads", arch->num_heads, 1, TG_MAXC));
+  if (arch->latent_dim != TG_HD * arch->num_heads)
+    return fail(TAMF_ERR_INVALID, "the head dimension must be 64: latent_dim = 64 * num_heads, got latent_dim " + std::to_string(arch->latent_dim) +
+                                      " with " + std::to_string(arch->num_heads) + " heads");
+  if (arch->ff_size < 16 || arch->ff_size > 4096 || arch->ff_size % 16)
+    return fail(TAMF_ERR_INVALID, "ff_size must be a multiple of 16 in [16, 4096], got " + std::to_string(arch->ff_size));
+  if (arch->num_layers < 1 || arch->num_layers > 64) return fail(TAMF_ERR_INVALID, range("num_layers", arch->num_layers, 1, 64));
+  const std::pair<const char*, int> widths[] = {{"input_dim", arch->input_dim}, {"obj_input_dim", arch->obj_input_dim}, {"hand_shape_dim", arch->hand_shape_dim},
+                                                {"obj_embed_dim", arch->obj_embed_dim}, {"h2o_dim", arch->h2o_dim}};
+  for (const auto& kv : widths)
+    if (kv.second < 1 || kv.second > 4096) return fail(TAMF_ERR_INVALID, range(kv.first, kv.second, 1, 4096));
+  if (max_frames < 1 || max_frames > MAX_S - PREFIX) return fail(TAMF_ERR_INVALID, range("max_frames", max_frames, 1, MAX_S - PREFIX));
+  if (max_batch < 1 || max_batch > 65535) return fail(TAMF_ERR_INVALID, range("max_batch", max_batch, 1, 65535));
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+
+  tamf_refinetrain_ctx* c = new (std::nothrow) tamf_refinetrain_ctx();
+  if (!c) return fail(TAMF_ERR_NOMEM, "out of host memory");
+  c->arch = *arch;
+  c->maxB = max_batch;
+  c->maxT = max_frames;
+  c->device = device;
+  declare_model(c);
+  const Dims n = dims(*arch, max_batch, max_frames);
+  Carver cv;
+  c->in = carve_input(cv, n);
+  for (int l = 0; l < arch->num_layers; ++l) c->lw.push_back(carve_layer(cv, n));
+  c->hw = carve_head(cv, n);
+  c->g = carve_grads(cv, n, c->slab_nk);
+  e = hipMalloc((void**)&c->ws, cv.total * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&c->cnt, n.B * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&c->clip, n.B * sizeof(long long));
+  if (e != hipSuccess) {
+    const std::string msg = std::string("hipMalloc of the workspace (") + std::to_string(cv.total * sizeof(float)) + " bytes): " + hipGetErrorString(e);
+    tamf_refinetrain_destroy(c);
+    return fail(e == hipErrorOutOfMemory ? TAMF_ERR_NOMEM : TAMF_ERR_HIP, msg);
+  }
+  *out = c;
+  return 0;
+}
+
+void tamf_refinetrain_destroy(tamf_refinetrain_ctx* c) {
+  if (!c) return;
+  for (auto& m : c->marks) (void)hipEventDestroy(std::get<1>(m)), (void)hipEventDestroy(std::get<2>(m));
+  if (c->ws) (void)hipFree(c->ws);
+  if (c->cnt) (void)hipFree(c->cnt);
+  if (c->clip) (void)hipFree(c->clip);
+  delete c;
+}
+
+int tamf_refinetrain_bind(tamf_refinetrain_ctx* c, const char* name, const float* param_dev, float* grad_dev, const int64_t* shape, int32_t ndim) {
+  if (!c || !name || !param_dev || ndim < 0 || (ndim > 0 && !shape)) return fail(TAMF_ERR_INVALID, "null argument");
+  Bound* b = find_declared(c->t, name, shape, ndim);
+  if (!b) return TAMF_ERR_INVALID;
+  if (b->trainable && !grad_dev) return fail(TAMF_ERR_INVALID, std::string(name) + ": a trainable tensor needs a gradient buffer");
+  if (!b->trainable && grad_dev) return fail(TAMF_ERR_INVALID, std::string(name) + ": a buffer takes no gradient");
+  b->p = param_dev;
+  b->g = grad_dev;
+  return 0;
+}
+
+int tamf_refinetrain_forward(tamf_refinetrain_ctx* c, int32_t B, int32_t T, int32_t nobj, const int32_t* obj_num_host,
+                             const float* sample_pose_dev, const float* h2o_dist_dev, const float* shape_dev, const uint8_t* hand_side_dev,
+                             const float* obj_emb_dev, const float* obj_traj_dev, const int64_t* clip_id_host, float dropout_p, uint64_t seed,
+                             uint32_t step, float* refine_pose_out_dev, void* stream) {
+  if (!c || !sample_pose_dev || !h2o_dist_dev || !shape_dev || !hand_side_dev || !obj_emb_dev || !obj_traj_dev || !refine_pose_out_dev)
+    return fail(TAMF_ERR_INVALID, "null argument");
+  if (B < 1 || B > c->maxB) return fail(TAMF_ERR_INVALID, "B = " + std::to_string(B) + " outside [1, max_batch = " + std::to_string(c->maxB) + "]");
+  if (T < 1 || T > c->maxT) return fail(TAMF_ERR_INVALID, "T = " + std::to_string(T) + " outside [1, max_frames = " + std::to_string(c->maxT) + "]");
+  if (nobj < 1 || nobj > 4096) return fail(TAMF_ERR_INVALID, range("nobj", nobj, 1, 4096));
+  if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(TAMF_ERR_INVALID, "dropout_p must be in [0, 1)");
+  if (obj_num_host)
+    for (int b = 0; b < B; ++b)
+      if (obj_num_host[b] < 1 || obj_num_host[b] > nobj)
+        return fail(TAMF_ERR_INVALID, "obj_num[" + std::to_string(b) + "] = " + std::to_string(obj_num_host[b]) + " outside [1, nobj = " + std::to_string(nobj) + "]");
+  for (const auto* kv : c->order)  // every tensor has to be there before anything is launched
+    if (!kv->second.p) return fail(TAMF_ERR_MISSING, "missing binding '" + kv->first + "'");
+  c->have_forward = false;
+  hipError_t e = hipSetDevice(c->device);
+  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  hipStream_t st = (hipStream_t)stream;
+  if (obj_num_host) e = hipMemcpyAsync(c->cnt, obj_num_host, B * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && clip_id_host) e = hipMemcpyAsync(c->clip, clip_id_host, B * sizeof(long long), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+
+  c->B = B, c->T = T;
+  c->io = Batch{sample_pose_dev, h2o_dist_dev, shape_dev, obj_emb_dev, obj_traj_dev, hand_side_dev, obj_num_host ? c->cnt : nullptr, refine_pose_out_dev, nobj};
+  c->drop = make_drop(seed, step, dropout_p, clip_id_host ? c->clip : nullptr);
+  Step s = make_step(c, st);
+  s.forward_input();
+  for (int l = 0; l < c->arch.num_layers; ++l) s.forward_layer(l);
+  s.forward_head();
+  c->have_forward = s.err == hipSuccess;
+  return s.status();
+}
+
+int tamf_refinetrain_backward(tamf_refinetrain_ctx* c, const float* grad_refine_pose_dev, void* stream) {
+  if (!c || !grad_refine_pose_dev) return fail(TAMF_ERR_INVALID, "null argument");
+  if (!c->have_forward) return fail(TAMF_ERR_STATE, "tamf_refinetrain_backward needs a preceding tamf_refinetrain_forward on this context (a forward serves one backward)");
+  for (const auto* kv : c->order)
+    if (!kv->second.p) return fail(TAMF_ERR_MISSING, "missing binding '" + kv->first + "'");
+  hipError_t e = hipSetDevice(c->device);
+  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  c->have_forward = false;
+  Step s = make_step(c, (hipStream_t)stream);
+  s.backward_head(grad_refine_pose_dev);
+  for (int l = c->arch.num_layers - 1; l >= 0; --l) s.backward_layer(l);
+  s.backward_input();
+  return s.status();
+}
+
+int tamf_refinetrain_set_profile(tamf_refinetrain_ctx* c, int32_t on) {
+  if (!c) return fail(TAMF_ERR_INVALID, "null argument");
+  c->profile = on != 0;
+  return 0;
+}
+
+int tamf_refinetrain_get_profile(tamf_refinetrain_ctx* c, char* out, int64_t size) {
+  if (!c || !out || size < 1) return fail(TAMF_ERR_INVALID, "null argument");
+  std::map<std::string, std::pair<long, double>> sum;  // name -> (launches, ms)
+  hipError_t e = hipSuccess;
+  for (auto& m : c->marks) {
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventSynchronize(std::get<2>(m));
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, std::get<1>(m), std::get<2>(m));
+    (void)hipEventDestroy(std::get<1>(m));
+    (void)hipEventDestroy(std::get<2>(m));
+    auto& s = sum[std::get<0>(m)];
+    s.first += 1;
+    s.second += ms;
+  }
+  c->marks.clear();
+  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("profile events: ") + hipGetErrorString(e));
+  std::string text;
+  for (const auto& kv : sum) text += kv.first + "\t" + std::to_string(kv.second.first) + "\t" + std::to_string(kv.second.second) + "\n";
+  if ((int64_t)text.size() + 1 > size) return fail(TAMF_ERR_INVALID, "the profile needs " + std::to_string(text.size() + 1) + " bytes");
+  std::copy(text.begin(), text.end(), out);
+  out[text.size()] = 0;
+  return 0;
+}
+
+int tamf_refinetrain_dropout_mask(uint64_t seed, uint32_t step, int64_t clip_id, int32_t site, int32_t rows, int32_t cols, float p,
+                                  uint8_t* out_dev, void* stream) {
+  if (!out_dev) return fail(TAMF_ERR_INVALID, "null argument");
+  if (rows < 1 || cols < 1 || (long)rows * cols > 0xFFFFFFFFL) return fail(TAMF_ERR_INVALID, "rows * cols must be in [1, 2^32)");
+  if (site < 0) return fail(TAMF_ERR_INVALID, "site must be >= 0");
+  if (!(p >= 0.f && p < 1.f)) return fail(TAMF_ERR_INVALID, "p must be in [0, 1)");
+  Step s;
+  s.st = (hipStream_t)stream;
+  const long n = (long)rows * cols;
+  s.launch(dropout_mask_kernel, blocks(n, 256), 256, 0, make_drop(seed, step, p, nullptr), site, (unsigned long long)clip_id, n, out_dev);
+  return s.status();
+}
+
+}  // extern "C"

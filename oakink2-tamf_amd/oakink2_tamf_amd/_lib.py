@@ -10,6 +10,7 @@ that description:
   TEXTENC  csrc/tamf_textenc.hip -> libtamf_textenc.so (include/tamf_textenc.h: the CLIP text tower behind text_embedding)
   ENCTRAIN csrc/tamf_enctrain.hip -> libtamf_enctrain.so (include/tamf_enctrain.h: the SegmentEncoder training step - forward, loss, gradients)
   CONTACT  csrc/tamf_contact.hip -> libtamf_contact.so (include/tamf_contact.h: the contact-distance kernels of the training losses)
+  REFINETRAIN csrc/tamf_refinetrain.hip -> libtamf_refinetrain.so (include/tamf_refinetrain.h: the SegmentRefineModel training step - forward, backward)
 POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
 score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
 Every library has its own sources, stamp and lock: building or loading one never touches another."""
@@ -35,6 +36,7 @@ POINTENC_LIB_PATH = os.path.join(LIB_DIR, "libtamf_pointenc.so")
 TEXTENC_LIB_PATH = os.path.join(LIB_DIR, "libtamf_textenc.so")
 ENCTRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_enctrain.so")
 CONTACT_LIB_PATH = os.path.join(LIB_DIR, "libtamf_contact.so")
+REFINETRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_refinetrain.so")
 
 EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_ctx_create", "tamf_ctx_resize", "tamf_ctx_destroy", "tamf_last_error", "tamf_load_weight", "tamf_finalize_weights",
@@ -69,6 +71,10 @@ ENCTRAIN_EXPORTS = [  # include/tamf_enctrain.h: what libtamf_enctrain.so export
 ]
 CONTACT_EXPORTS = [  # include/tamf_contact.h: what libtamf_contact.so exports
     "tamf_contact_last_error", "tamf_contact_forward", "tamf_contact_backward",
+]
+REFINETRAIN_EXPORTS = [  # include/tamf_refinetrain.h: what libtamf_refinetrain.so exports
+    "tamf_refinetrain_last_error", "tamf_refinetrain_create", "tamf_refinetrain_destroy", "tamf_refinetrain_bind", "tamf_refinetrain_forward",
+    "tamf_refinetrain_backward", "tamf_refinetrain_dropout_mask", "tamf_refinetrain_set_profile", "tamf_refinetrain_get_profile",
 ]
 
 
@@ -273,15 +279,20 @@ ENCTRAIN = Library("libtamf_enctrain", "tamf_enctrain.hip", ("tamf_enctrain.h", 
 CONTACT = Library("libtamf_contact", "tamf_contact.hip", ("tamf_contact.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
                   (Output("libtamf_contact.so", (), CONTACT_EXPORTS),),
                   kernels=("_Z18contact_h2o_kernel", "_Z18contact_o2h_kernel", "_Z23contact_backward_kernel"))
+REFINETRAIN = Library("libtamf_refinetrain", "tamf_refinetrain.hip", ("tamf_refinetrain.h", "tamf_hip.h"),  # (tamf_hip.h for tamf_status and tamf_arch)
+                      (Output("libtamf_refinetrain.so", (), REFINETRAIN_EXPORTS),),
+                      kernels=("_Z13tg_lin_kernelILb0EE", "_Z13tg_lin_kernelILb1EE", "_Z15tg_wgrad_kernel", "_Z18tg_attn_fwd_kernel", "_Z20tg_attn_bwd_q_kernel",
+                               "_Z21tg_attn_bwd_kv_kernel"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)
 TRAINING = (ENCTRAIN, CONTACT)  # the SegmentEncoder training step (launch/train_encoder.py); the contact-distance losses (contact.py)
+REFINE_TRAINING = (REFINETRAIN,)  # the refiner's training step (model/segment_refine_train.py); a group of its own: tests pin TRAINING to two
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Every library, the sampler pair first, each only when ITS sources changed.  One library at a time.  Returns LIB_PATH."""
-    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING:
+    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING:
         lib.build(force, verbose)
     return LIB_PATH
 
@@ -348,6 +359,11 @@ def load_enctrain() -> ctypes.CDLL:
 def load_contact() -> ctypes.CDLL:
     """libtamf_contact.so (include/tamf_contact.h).  Independent of the other libraries."""
     return _load(CONTACT, "libtamf_contact.so")
+
+
+def load_refinetrain() -> ctypes.CDLL:
+    """libtamf_refinetrain.so (include/tamf_refinetrain.h).  Independent of the other libraries."""
+    return _load(REFINETRAIN, "libtamf_refinetrain.so")
 
 
 def load_from(path: str) -> ctypes.CDLL:
