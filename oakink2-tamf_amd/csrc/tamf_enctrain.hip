@@ -1,10 +1,11 @@
-// libtamf_enctrain.so (include/tamf_enctrain.h): the host side of the SegmentEncoder training step - the table of bound tensors, the
-// workspace and the launch sequence of the kernels of tamf_encoder_grad.h.  Host conventions of tamf_weights.h: an int status, a
-// thread-local last-error string, nothing thrown across the ABI.
+// libtamf_enctrain.so (include/tamf_enctrain.h): the host side of the SegmentEncoder training step - the declared tensors, the
+// workspace and the launch sequence of the kernels of tamf_encoder_grad.h, on the host code of tamf_train_host.h (the table, the
+// context base, the call checks, the launcher).  Host conventions of tamf_weights.h: an int status, a thread-local last-error string,
+// nothing thrown across the ABI.
 //
 // Row counts of the workspace structs below: R = B (T + 4) token rows (3 prefix rows, T frames, the classification row of every clip),
 // BT = B T frame rows; the context carves them for (max_batch, max_frames), a step addresses them with its own B and T.
-#include "tamf_weights.h"
+#include "tamf_train_host.h"
 
 #include "../../include/tamf_enctrain.h"
 #include "tamf_encoder_grad.h"
@@ -12,21 +13,6 @@
 namespace {
 
 constexpr int MAX_SPLIT = 64, SPLIT_ROWS = 128, D = ENC_D;
-
-struct Bound {
-  std::vector<int64_t> shape;
-  bool trainable = true;
-  const float* p = nullptr;
-  float* g = nullptr;
-};
-// one declared (weight, bias) pair, N x K and N, where it is bound - a linear map, or the gain and bias of a LayerNorm (K = 0)
-struct Lin {
-  const Bound *w = nullptr, *b = nullptr;
-  int N = 0, K = 0;
-};
-struct LayerP {
-  Lin inproj, out, l1, l2, n1, n2;
-};
 
 struct Dims {
   long B, BT, R;
@@ -49,22 +35,6 @@ InputWs carve_input(Carver& cv, const Dims& n) {
   x.zpre = cv.take(n.BT * D);             // [BT][64]   the first merge map before ...
   x.z = cv.take(n.BT * D);                //            ... and after SiLU
   x.pre = cv.take(n.R * D);               // [R][64]    token rows before nan_to_num and PE
-  return x;
-}
-struct LayerWs {
-  long x, qkv, stat, att, x1pre, x1, x2pre, hpre, gel;
-};
-LayerWs carve_layer(Carver& cv, const Dims& n) {
-  LayerWs x;
-  x.x = cv.take(n.R * D);                 // [R][64]       the layer's input
-  x.qkv = cv.take(n.R * 3 * D);           // [R][192]
-  x.stat = cv.take(n.R * EG_H * 2);       // [B][4][S][2]  softmax (max, sum)
-  x.att = cv.take(n.R * D);               // [R][64]       attention output
-  x.x1pre = cv.take(n.R * D);             // [R][64]       LayerNorm 1: input,
-  x.x1 = cv.take(n.R * D);                //               output
-  x.x2pre = cv.take(n.R * D);             // [R][64]       LayerNorm 2: input (its output is the next layer's x)
-  x.hpre = cv.take(n.R * n.ff);           // [R][ff]       the feed-forward hidden rows before GELU,
-  x.gel = cv.take(n.R * n.ff);            //               after GELU and dropout
   return x;
 }
 struct HeadWs {
@@ -106,18 +76,11 @@ GradWs carve_grads(Carver& cv, const Dims& n, long slab_nk) {
 
 }  // namespace
 
-struct tamf_enctrain_ctx {
-  tamf_arch arch;
-  int maxB, maxT, device;
-  std::map<std::string, Bound> t;                                      // (nodes are address-stable: Lin points into them)
-  std::vector<const std::pair<const std::string, Bound>*> order;       // in declaration order
-  long slab_nk = 0;                                                    // the largest N (K + 1) of a declared linear map
+struct tamf_enctrain_ctx : TrainCtx {
+  using TrainCtx::TrainCtx;
   const Bound *rh, *lh, *cls, *pe;
   Lin shape, obj, pose, traj, m0, m2, p0, p2, p4;
   std::vector<LayerP> lp;
-  float* ws = nullptr;
-  int* cnt = nullptr;         // [maxB]
-  long long* clip = nullptr;  // [maxB]
   InputWs in;
   std::vector<LayerWs> lw;
   HeadWs head;
@@ -126,51 +89,25 @@ struct tamf_enctrain_ctx {
 
 namespace {
 
-const Bound* declare(tamf_enctrain_ctx* c, const std::string& k, std::vector<int64_t> shape, bool trainable = true) {
-  auto it = c->t.emplace(k, Bound{std::move(shape), trainable}).first;
-  c->order.push_back(&*it);
-  return &it->second;
-}
-Lin declare_pair(tamf_enctrain_ctx* c, const std::string& wk, const std::string& bk, int o, int i) {
-  c->slab_nk = std::max(c->slab_nk, (long)o * (i + 1));
-  const Bound* w = declare(c, wk, {o, i});
-  return Lin{w, declare(c, bk, {o}), o, i};
-}
-Lin declare_linear(tamf_enctrain_ctx* c, const std::string& k, int o, int i) { return declare_pair(c, k + ".weight", k + ".bias", o, i); }
-Lin declare_norm(tamf_enctrain_ctx* c, const std::string& k) {
-  const Bound* w = declare(c, k + ".weight", {D});
-  return Lin{w, declare(c, k + ".bias", {D}), D, 0};
-}
 // every tensor of the state dict, in its order
 void declare_model(tamf_enctrain_ctx* c) {
   const tamf_arch& a = c->arch;
-  c->rh = declare(c, "hand_side_process.rh_embed", {D}, false);
-  c->lh = declare(c, "hand_side_process.lh_embed", {D}, false);
-  c->shape = declare_linear(c, "hand_shape_process.shape_embed", D, a.hand_shape_dim);
-  c->obj = declare_linear(c, "obj_embed_process.embedding", D, a.obj_embed_dim);
-  c->cls = declare(c, "classification_token", {1, 1, D}, false);
-  c->pose = declare_linear(c, "input_process.poseEmbedding", D, a.input_dim);
-  c->traj = declare_linear(c, "obj_input_process.poseEmbedding", D, a.obj_input_dim);
-  c->m0 = declare_linear(c, "input_merge.0", D, 2 * D);
-  c->m2 = declare_linear(c, "input_merge.2", D, D);
-  c->pe = declare(c, "sequence_pos_encoder.pe", {5000, 1, D}, false);
-  c->lp.resize(a.num_layers);
-  for (int l = 0; l < a.num_layers; ++l) {
-    const std::string p = "seqTransEncoder.layers." + std::to_string(l) + ".";
-    LayerP& x = c->lp[l];
-    x.inproj = declare_pair(c, p + "self_attn.in_proj_weight", p + "self_attn.in_proj_bias", 3 * D, D);
-    x.out = declare_linear(c, p + "self_attn.out_proj", D, D);
-    x.l1 = declare_linear(c, p + "linear1", a.ff_size, D);
-    x.l2 = declare_linear(c, p + "linear2", D, a.ff_size);
-    x.n1 = declare_norm(c, p + "norm1");
-    x.n2 = declare_norm(c, p + "norm2");
-  }
-  c->p0 = declare_linear(c, "output_process.poseFinal.0", D, D);
-  c->p2 = declare_linear(c, "output_process.poseFinal.2", D, D);
-  c->p4 = declare_linear(c, "output_process.poseFinal.4", a.input_dim, D);
+  ParamTable& t = c->tab;
+  c->rh = t.declare("hand_side_process.rh_embed", {D}, false);
+  c->lh = t.declare("hand_side_process.lh_embed", {D}, false);
+  c->shape = t.declare_linear("hand_shape_process.shape_embed", D, a.hand_shape_dim);
+  c->obj = t.declare_linear("obj_embed_process.embedding", D, a.obj_embed_dim);
+  c->cls = t.declare("classification_token", {1, 1, D}, false);
+  c->pose = t.declare_linear("input_process.poseEmbedding", D, a.input_dim);
+  c->traj = t.declare_linear("obj_input_process.poseEmbedding", D, a.obj_input_dim);
+  c->m0 = t.declare_linear("input_merge.0", D, 2 * D);
+  c->m2 = t.declare_linear("input_merge.2", D, D);
+  c->pe = t.declare("sequence_pos_encoder.pe", {5000, 1, D}, false);
+  for (int l = 0; l < a.num_layers; ++l) c->lp.push_back(t.declare_layer(l, D, a.ff_size));
+  c->p0 = t.declare_linear("output_process.poseFinal.0", D, D);
+  c->p2 = t.declare_linear("output_process.poseFinal.2", D, D);
+  c->p4 = t.declare_linear("output_process.poseFinal.4", a.input_dim, D);
 }
-
-RowMap flat(long ld) { return RowMap{ROWMAP_FLAT, 0, ld}; }
 
 // the epilogue of a lin_kernel launch: an EgMode with the operands that mode reads
 struct Epi {
@@ -204,34 +141,18 @@ struct LayerView {
   long o64, off;        // from these offsets
 };
 
-struct Step {
+struct Step : StepRows {
   tamf_enctrain_ctx* c = nullptr;
-  hipStream_t st = nullptr;
   Dims n{};
-  int B = 0, T = 0, S = 0;
   Batch io{};
   Drop drop{};
-  hipError_t err = hipSuccess;
 
-  float* w(long off) const { return c->ws + off; }
-  float* xof(int l) const { return w(l < (int)c->lw.size() ? c->lw[l].x : c->head.xlast); }  // layer l's input; xof(L): the output
-  RowMap rows(int nq, long ld) const { return RowMap{nq, (long)S * ld, ld}; }  // nq rows of every clip inside [B][S][ld]
-  RowMap one() const { return rows(1, D); }
-  RowMap frames() const { return rows(T, D); }
   float* cls_rows() const { return xof((int)c->lw.size()) + (long)(S - 1) * D; }  // the encoder's classification rows, at one()
   size_t att_lds() const { return (size_t)S * ENC_HD * 2 * sizeof(float); }
   LayerView layer_view(int l) const {
     const int q0 = l == (int)c->lw.size() - 1 ? S - 1 : 0, nq = S - q0;
     return {q0, nq, B * nq, 1 + 4 * l, rows(nq, D), rows(nq, n.ff), (long)q0 * D, (long)q0 * n.ff};
   }
-
-  // every launch of the library: the first launch error is kept
-  template <class K, class... A>
-  void launch(K kernel, dim3 grid, int block, size_t lds, A... args) {
-    kernel<<<grid, block, lds, st>>>(args...);
-    if (err == hipSuccess) err = hipGetLastError();
-  }
-  int status() const { return err == hipSuccess ? 0 : fail(TAMF_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(err)); }
 
   void lin(LinArgs a, const Epi& e) {
     a.rm = a.cm;
@@ -388,26 +309,18 @@ int tamf_enctrain_create(const tamf_arch* arch, int32_t max_batch, int32_t max_f
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
 
-  tamf_enctrain_ctx* c = new (std::nothrow) tamf_enctrain_ctx();
+  tamf_enctrain_ctx* c = new (std::nothrow) tamf_enctrain_ctx(*arch, max_batch, max_frames, device);
   if (!c) return fail(TAMF_ERR_NOMEM, "out of host memory");
-  c->arch = *arch;
-  c->maxB = max_batch;
-  c->maxT = max_frames;
-  c->device = device;
   declare_model(c);
   const Dims n = dims(*arch, max_batch, max_frames);
   Carver cv;
   c->in = carve_input(cv, n);
-  for (int l = 0; l < arch->num_layers; ++l) c->lw.push_back(carve_layer(cv, n));
+  for (int l = 0; l < arch->num_layers; ++l) c->lw.push_back(carve_layer(cv, n.R, D, EG_H, n.ff));
   c->head = carve_head(cv, n);
-  c->g = carve_grads(cv, n, c->slab_nk);
-  e = hipMalloc((void**)&c->ws, cv.total * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&c->cnt, n.B * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc((void**)&c->clip, n.B * sizeof(long long));
-  if (e != hipSuccess) {
-    const std::string msg = std::string("hipMalloc of the workspace (") + std::to_string(cv.total * sizeof(float)) + " bytes): " + hipGetErrorString(e);
+  c->g = carve_grads(cv, n, c->tab.slab_nk);
+  if (int rc = alloc_buffers(c, cv)) {
     tamf_enctrain_destroy(c);
-    return fail(e == hipErrorOutOfMemory ? TAMF_ERR_NOMEM : TAMF_ERR_HIP, msg);
+    return rc;
   }
   *out = c;
   return 0;
@@ -415,21 +328,12 @@ int tamf_enctrain_create(const tamf_arch* arch, int32_t max_batch, int32_t max_f
 
 void tamf_enctrain_destroy(tamf_enctrain_ctx* c) {
   if (!c) return;
-  if (c->ws) (void)hipFree(c->ws);
-  if (c->cnt) (void)hipFree(c->cnt);
-  if (c->clip) (void)hipFree(c->clip);
+  free_buffers(c);
   delete c;
 }
 
 int tamf_enctrain_bind(tamf_enctrain_ctx* c, const char* name, const float* param_dev, float* grad_dev, const int64_t* shape, int32_t ndim) {
-  if (!c || !name || !param_dev || ndim < 0 || (ndim > 0 && !shape)) return fail(TAMF_ERR_INVALID, "null argument");
-  Bound* b = find_declared(c->t, name, shape, ndim);
-  if (!b) return TAMF_ERR_INVALID;
-  if (b->trainable && !grad_dev) return fail(TAMF_ERR_INVALID, std::string(name) + ": a trainable tensor needs a gradient buffer");
-  if (!b->trainable && grad_dev) return fail(TAMF_ERR_INVALID, std::string(name) + ": a buffer takes no gradient");
-  b->p = param_dev;
-  b->g = grad_dev;
-  return 0;
+  return bind_declared(c ? &c->tab : nullptr, name, param_dev, grad_dev, shape, ndim);
 }
 
 int tamf_enctrain_step(tamf_enctrain_ctx* c, int32_t B, int32_t T, int32_t nobj, const int32_t* obj_num_host, const float* pose_dev,
@@ -438,28 +342,15 @@ int tamf_enctrain_step(tamf_enctrain_ctx* c, int32_t B, int32_t T, int32_t nobj,
                        float* loss_out_dev, float* activation_out_dev, void* stream) {
   if (!c || !pose_dev || !shape_dev || !hand_side_dev || !obj_emb_dev || !obj_traj_dev || !labels_dev || !loss_out_dev || !activation_out_dev)
     return fail(TAMF_ERR_INVALID, "null argument");
-  if (B < 1 || B > c->maxB) return fail(TAMF_ERR_INVALID, "B = " + std::to_string(B) + " outside [1, max_batch = " + std::to_string(c->maxB) + "]");
-  if (T < 1 || T > c->maxT) return fail(TAMF_ERR_INVALID, "T = " + std::to_string(T) + " outside [1, max_frames = " + std::to_string(c->maxT) + "]");
-  if (nobj < 1 || nobj > 4096) return fail(TAMF_ERR_INVALID, "nobj = " + std::to_string(nobj) + " outside [1, 4096]");
-  if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(TAMF_ERR_INVALID, "dropout_p must be in [0, 1)");
-  if (obj_num_host)
-    for (int b = 0; b < B; ++b)
-      if (obj_num_host[b] < 1 || obj_num_host[b] > nobj)
-        return fail(TAMF_ERR_INVALID, "obj_num[" + std::to_string(b) + "] = " + std::to_string(obj_num_host[b]) + " outside [1, nobj = " + std::to_string(nobj) + "]");
-  for (const auto* kv : c->order)  // every tensor has to be there before anything is launched
-    if (!kv->second.p) return fail(TAMF_ERR_MISSING, "missing binding '" + kv->first + "'");
-  hipError_t e = hipSetDevice(c->device);
-  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-  hipStream_t st = (hipStream_t)stream;
-  if (obj_num_host) e = hipMemcpyAsync(c->cnt, obj_num_host, B * sizeof(int), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && clip_id_host) e = hipMemcpyAsync(c->clip, clip_id_host, B * sizeof(long long), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+  if (int rc = check_call(c, B, T, nobj, dropout_p, obj_num_host)) return rc;
+  if (int rc = stage_call(c, B, obj_num_host, clip_id_host, (hipStream_t)stream)) return rc;
 
   Step s;
   s.c = c;
-  s.st = st;
+  s.st = (hipStream_t)stream;
+  s.ws = c->ws, s.lw = &c->lw, s.xlast = c->head.xlast;
   s.n = dims(c->arch, B, T);
-  s.B = B, s.T = T, s.S = T + ENC_P + 1;
+  s.B = B, s.T = T, s.S = T + ENC_P + 1, s.D = D;
   s.io = Batch{pose_dev, shape_dev, obj_emb_dev, obj_traj_dev, hand_side_dev, obj_num_host ? c->cnt : nullptr, (const long long*)labels_dev, loss_out_dev, activation_out_dev, nobj};
   s.drop = make_drop(seed, step, dropout_p, clip_id_host ? c->clip : nullptr);
   const int L = c->arch.num_layers;
@@ -474,15 +365,7 @@ int tamf_enctrain_step(tamf_enctrain_ctx* c, int32_t B, int32_t T, int32_t nobj,
 
 int tamf_enctrain_dropout_mask(uint64_t seed, uint32_t step, int64_t clip_id, int32_t site, int32_t rows, int32_t cols, float p,
                                uint8_t* out_dev, void* stream) {
-  if (!out_dev) return fail(TAMF_ERR_INVALID, "null argument");
-  if (rows < 1 || cols < 1 || (long)rows * cols > 0xFFFFFFFFL) return fail(TAMF_ERR_INVALID, "rows * cols must be in [1, 2^32)");
-  if (site < 0) return fail(TAMF_ERR_INVALID, "site must be >= 0");
-  if (!(p >= 0.f && p < 1.f)) return fail(TAMF_ERR_INVALID, "p must be in [0, 1)");
-  Step s;
-  s.st = (hipStream_t)stream;
-  const long n = (long)rows * cols;
-  s.launch(dropout_mask_kernel, blocks(n, 256), 256, 0, make_drop(seed, step, p, nullptr), site, (unsigned long long)clip_id, n, out_dev);
-  return s.status();
+  return dropout_mask(seed, step, clip_id, site, rows, cols, p, out_dev, stream);
 }
 
 }  // extern "C"

@@ -1,13 +1,14 @@
-// libtamf_refinetrain.so (include/tamf_refinetrain.h): the host side of the SegmentRefineModel training step - the table of bound
-// tensors, the workspace and the launch sequences of the kernels of tamf_trunk_grad.h.  Host conventions of tamf_weights.h: an int
-// status, a thread-local last-error string, nothing thrown across the ABI.
+// libtamf_refinetrain.so (include/tamf_refinetrain.h): the host side of the SegmentRefineModel training step - the declared tensors,
+// the workspace and the launch sequences of the kernels of tamf_trunk_grad.h, on the host code of tamf_train_host.h (the table, the
+// context base, the call checks, the launcher).  Host conventions of tamf_weights.h: an int status, a thread-local last-error string,
+// nothing thrown across the ABI.
 //
 // The layer stack (forward_layer / backward_layer) sees token rows [B][S][d] and nothing of the model around it; the refiner is its
 // input stage (3 prefix rows, frames merged from pose | object trajectory | hand->object distance) and its head (x_in + poseFinal).
 //
 // Row counts of the workspace structs below: R = B (T + 3) token rows, BT = B T frame rows; the context carves them for (max_batch,
 // max_frames), a call addresses them with its own B and T.
-#include "tamf_weights.h"
+#include "tamf_train_host.h"
 
 #include <tuple>
 
@@ -17,21 +18,6 @@
 namespace {
 
 constexpr int MAX_SPLIT = 64, SPLIT_ROWS = 256, PREFIX = 3, MAX_S = 1024;
-
-struct Bound {
-  std::vector<int64_t> shape;
-  bool trainable = true;
-  const float* p = nullptr;
-  float* g = nullptr;
-};
-// one declared (weight, bias) pair, N x K and N, where it is bound - a linear map, or the gain and bias of a LayerNorm (K = 0)
-struct Lin {
-  const Bound *w = nullptr, *b = nullptr;
-  int N = 0, K = 0;
-};
-struct LayerP {
-  Lin inproj, out, l1, l2, n1, n2;
-};
 
 struct Dims {
   long B, BT, R;
@@ -54,22 +40,6 @@ InputWs carve_input(Carver& cv, const Dims& n) {
   x.zpre = cv.take(n.BT * n.D);           // [BT][d]     the first merge map before ...
   x.z = cv.take(n.BT * n.D);              //             ... and after SiLU
   x.pre = cv.take(n.R * n.D);             // [R][d]      token rows before nan_to_num and PE
-  return x;
-}
-struct LayerWs {
-  long x, qkv, stat, att, x1pre, x1, x2pre, hpre, gel;
-};
-LayerWs carve_layer(Carver& cv, const Dims& n) {
-  LayerWs x;
-  x.x = cv.take(n.R * n.D);               // [R][d]        the layer's input
-  x.qkv = cv.take(n.R * 3 * n.D);         // [R][3 d]
-  x.stat = cv.take(n.R * n.H * 2);        // [B][H][S][2]  softmax (max, sum)
-  x.att = cv.take(n.R * n.D);             // [R][d]        attention output
-  x.x1pre = cv.take(n.R * n.D);           // [R][d]        LayerNorm 1: input,
-  x.x1 = cv.take(n.R * n.D);              //               output
-  x.x2pre = cv.take(n.R * n.D);           // [R][d]        LayerNorm 2: input (its output is the next layer's x)
-  x.hpre = cv.take(n.R * n.ff);           // [R][ff]       the feed-forward hidden rows before GELU,
-  x.gel = cv.take(n.R * n.ff);            //               after GELU and dropout
   return x;
 }
 struct HeadWs {
@@ -114,18 +84,11 @@ struct Batch {
 
 }  // namespace
 
-struct tamf_refinetrain_ctx {
-  tamf_arch arch;
-  int maxB, maxT, device;
-  std::map<std::string, Bound> t;                                      // (nodes are address-stable: Lin points into them)
-  std::vector<const std::pair<const std::string, Bound>*> order;       // in declaration order
-  long slab_nk = 0;                                                    // the largest N (K + 1) of a declared linear map
+struct tamf_refinetrain_ctx : TrainCtx {
+  using TrainCtx::TrainCtx;
   const Bound *rh, *lh, *pe;
   Lin shape, obj, pose, traj, dist, m0, m2, head;
   std::vector<LayerP> lp;
-  float* ws = nullptr;
-  int* cnt = nullptr;         // [maxB]
-  long long* clip = nullptr;  // [maxB]
   InputWs in;
   std::vector<LayerWs> lw;
   HeadWs hw;
@@ -142,50 +105,24 @@ struct tamf_refinetrain_ctx {
 
 namespace {
 
-const Bound* declare(tamf_refinetrain_ctx* c, const std::string& k, std::vector<int64_t> shape, bool trainable = true) {
-  auto it = c->t.emplace(k, Bound{std::move(shape), trainable}).first;
-  c->order.push_back(&*it);
-  return &it->second;
-}
-Lin declare_pair(tamf_refinetrain_ctx* c, const std::string& wk, const std::string& bk, int o, int i) {
-  c->slab_nk = std::max(c->slab_nk, (long)o * (i + 1));
-  const Bound* w = declare(c, wk, {o, i});
-  return Lin{w, declare(c, bk, {o}), o, i};
-}
-Lin declare_linear(tamf_refinetrain_ctx* c, const std::string& k, int o, int i) { return declare_pair(c, k + ".weight", k + ".bias", o, i); }
-Lin declare_norm(tamf_refinetrain_ctx* c, const std::string& k, int D) {
-  const Bound* w = declare(c, k + ".weight", {D});
-  return Lin{w, declare(c, k + ".bias", {D}), D, 0};
-}
 // every tensor of the state dict, in its order
 void declare_model(tamf_refinetrain_ctx* c) {
   const tamf_arch& a = c->arch;
+  ParamTable& t = c->tab;
   const int D = a.latent_dim;
-  c->rh = declare(c, "hand_side_process.rh_embed", {D}, false);
-  c->lh = declare(c, "hand_side_process.lh_embed", {D}, false);
-  c->shape = declare_linear(c, "hand_shape_process.shape_embed", D, a.hand_shape_dim);
-  c->obj = declare_linear(c, "obj_embed_process.embedding", D, a.obj_embed_dim);
-  c->pose = declare_linear(c, "input_process.poseEmbedding", D, a.input_dim);
-  c->traj = declare_linear(c, "obj_input_process.poseEmbedding", D, a.obj_input_dim);
-  c->dist = declare_linear(c, "h2o_dist_input_process.poseEmbedding", D, a.h2o_dim);
-  c->m0 = declare_linear(c, "input_merge.0", D, 3 * D);
-  c->m2 = declare_linear(c, "input_merge.2", D, D);
-  c->pe = declare(c, "sequence_pos_encoder.pe", {5000, 1, D}, false);
-  c->lp.resize(a.num_layers);
-  for (int l = 0; l < a.num_layers; ++l) {
-    const std::string p = "seqTransEncoder.layers." + std::to_string(l) + ".";
-    LayerP& x = c->lp[l];
-    x.inproj = declare_pair(c, p + "self_attn.in_proj_weight", p + "self_attn.in_proj_bias", 3 * D, D);
-    x.out = declare_linear(c, p + "self_attn.out_proj", D, D);
-    x.l1 = declare_linear(c, p + "linear1", a.ff_size, D);
-    x.l2 = declare_linear(c, p + "linear2", D, a.ff_size);
-    x.n1 = declare_norm(c, p + "norm1", D);
-    x.n2 = declare_norm(c, p + "norm2", D);
-  }
-  c->head = declare_linear(c, "output_process.poseFinal", a.input_dim, D);
+  c->rh = t.declare("hand_side_process.rh_embed", {D}, false);
+  c->lh = t.declare("hand_side_process.lh_embed", {D}, false);
+  c->shape = t.declare_linear("hand_shape_process.shape_embed", D, a.hand_shape_dim);
+  c->obj = t.declare_linear("obj_embed_process.embedding", D, a.obj_embed_dim);
+  c->pose = t.declare_linear("input_process.poseEmbedding", D, a.input_dim);
+  c->traj = t.declare_linear("obj_input_process.poseEmbedding", D, a.obj_input_dim);
+  c->dist = t.declare_linear("h2o_dist_input_process.poseEmbedding", D, a.h2o_dim);
+  c->m0 = t.declare_linear("input_merge.0", D, 3 * D);
+  c->m2 = t.declare_linear("input_merge.2", D, D);
+  c->pe = t.declare("sequence_pos_encoder.pe", {5000, 1, D}, false);
+  for (int l = 0; l < a.num_layers; ++l) c->lp.push_back(t.declare_layer(l, D, a.ff_size));
+  c->head = t.declare_linear("output_process.poseFinal", a.input_dim, D);
 }
-
-RowMap flat(long ld) { return RowMap{ROWMAP_FLAT, 0, ld}; }
 
 // the epilogue of a tg_lin_kernel launch: a TgMode with the operands that mode reads
 struct Epi {
@@ -259,37 +196,27 @@ __global__ void finite_mask_kernel(const float* pre, const float* dout, float* d
   dpre[e] = (v - v == 0.f) ? dout[e] : 0.f;
 }
 
-struct Step {
+struct Step : StepRows {
   tamf_refinetrain_ctx* c = nullptr;
-  hipStream_t st = nullptr;
   Dims n{};
-  int B = 0, T = 0, S = 0, D = 0;
   Batch io{};
   Drop drop{};
-  hipError_t err = hipSuccess;
   const char* tag = "other";  // what the next launches are called in the profile
 
-  float* w(long off) const { return c->ws + off; }
-  float* xof(int l) const { return w(l < (int)c->lw.size() ? c->lw[l].x : c->hw.xlast); }  // layer l's input; xof(L): the output
-  RowMap rows(int nq, long ld) const { return RowMap{nq, (long)S * ld, ld}; }  // nq rows of every clip inside [B][S][ld]
-  RowMap tok(long ld) const { return rows(S, ld); }                            // every token row, split into (clip, row)
-  RowMap one() const { return rows(1, D); }
-  RowMap frames() const { return rows(T, D); }
+  RowMap tok(long ld) const { return rows(S, ld); }  // every token row, split into (clip, row)
 
-  // every launch of the library: the first launch error is kept
+  // the shared launch, between a pair of events when the context's profile is on
   template <class K, class... A>
   void launch(K kernel, dim3 grid, int block, size_t lds, A... args) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timed = c && c->profile && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    const bool timed = c->profile && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
     if (timed) (void)hipEventRecord(e0, st);
-    kernel<<<grid, block, lds, st>>>(args...);
-    if (err == hipSuccess) err = hipGetLastError();
+    Launcher::launch(kernel, grid, block, lds, args...);
     if (timed) {
       (void)hipEventRecord(e1, st);
       c->marks.emplace_back(tag, e0, e1);
     }
   }
-  int status() const { return err == hipSuccess ? 0 : fail(TAMF_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(err)); }
 
   void lin(TgLin a, const Epi& e, bool wt) {
     a.rm = a.cm;
@@ -439,15 +366,12 @@ Step make_step(tamf_refinetrain_ctx* c, hipStream_t st) {
   Step s;
   s.c = c;
   s.st = st;
+  s.ws = c->ws, s.lw = &c->lw, s.xlast = c->hw.xlast;
   s.n = dims(c->arch, c->B, c->T);
   s.B = c->B, s.T = c->T, s.S = c->T + PREFIX, s.D = c->arch.latent_dim;
   s.io = c->io;
   s.drop = c->drop;
   return s;
-}
-
-std::string range(const char* what, long v, long lo, long hi) {
-  return std::string(what) + " = " + std::to_string(v) + " outside [" + std::to_string(lo) + ", " + std::to_string(hi) + "]";
 }
 
 }  // namespace
@@ -475,26 +399,18 @@ int tamf_refinetrain_create(const tamf_arch* arch, int32_t max_batch, int32_t ma
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
 
-  tamf_refinetrain_ctx* c = new (std::nothrow) tamf_refinetrain_ctx();
+  tamf_refinetrain_ctx* c = new (std::nothrow) tamf_refinetrain_ctx(*arch, max_batch, max_frames, device);
   if (!c) return fail(TAMF_ERR_NOMEM, "out of host memory");
-  c->arch = *arch;
-  c->maxB = max_batch;
-  c->maxT = max_frames;
-  c->device = device;
   declare_model(c);
   const Dims n = dims(*arch, max_batch, max_frames);
   Carver cv;
   c->in = carve_input(cv, n);
-  for (int l = 0; l < arch->num_layers; ++l) c->lw.push_back(carve_layer(cv, n));
+  for (int l = 0; l < arch->num_layers; ++l) c->lw.push_back(carve_layer(cv, n.R, n.D, n.H, n.ff));
   c->hw = carve_head(cv, n);
-  c->g = carve_grads(cv, n, c->slab_nk);
-  e = hipMalloc((void**)&c->ws, cv.total * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&c->cnt, n.B * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc((void**)&c->clip, n.B * sizeof(long long));
-  if (e != hipSuccess) {
-    const std::string msg = std::string("hipMalloc of the workspace (") + std::to_string(cv.total * sizeof(float)) + " bytes): " + hipGetErrorString(e);
+  c->g = carve_grads(cv, n, c->tab.slab_nk);
+  if (int rc = alloc_buffers(c, cv)) {
     tamf_refinetrain_destroy(c);
-    return fail(e == hipErrorOutOfMemory ? TAMF_ERR_NOMEM : TAMF_ERR_HIP, msg);
+    return rc;
   }
   *out = c;
   return 0;
@@ -503,21 +419,12 @@ int tamf_refinetrain_create(const tamf_arch* arch, int32_t max_batch, int32_t ma
 void tamf_refinetrain_destroy(tamf_refinetrain_ctx* c) {
   if (!c) return;
   for (auto& m : c->marks) (void)hipEventDestroy(std::get<1>(m)), (void)hipEventDestroy(std::get<2>(m));
-  if (c->ws) (void)hipFree(c->ws);
-  if (c->cnt) (void)hipFree(c->cnt);
-  if (c->clip) (void)hipFree(c->clip);
+  free_buffers(c);
   delete c;
 }
 
 int tamf_refinetrain_bind(tamf_refinetrain_ctx* c, const char* name, const float* param_dev, float* grad_dev, const int64_t* shape, int32_t ndim) {
-  if (!c || !name || !param_dev || ndim < 0 || (ndim > 0 && !shape)) return fail(TAMF_ERR_INVALID, "null argument");
-  Bound* b = find_declared(c->t, name, shape, ndim);
-  if (!b) return TAMF_ERR_INVALID;
-  if (b->trainable && !grad_dev) return fail(TAMF_ERR_INVALID, std::string(name) + ": a trainable tensor needs a gradient buffer");
-  if (!b->trainable && grad_dev) return fail(TAMF_ERR_INVALID, std::string(name) + ": a buffer takes no gradient");
-  b->p = param_dev;
-  b->g = grad_dev;
-  return 0;
+  return bind_declared(c ? &c->tab : nullptr, name, param_dev, grad_dev, shape, ndim);
 }
 
 int tamf_refinetrain_forward(tamf_refinetrain_ctx* c, int32_t B, int32_t T, int32_t nobj, const int32_t* obj_num_host,
@@ -526,23 +433,10 @@ int tamf_refinetrain_forward(tamf_refinetrain_ctx* c, int32_t B, int32_t T, int3
                              uint32_t step, float* refine_pose_out_dev, void* stream) {
   if (!c || !sample_pose_dev || !h2o_dist_dev || !shape_dev || !hand_side_dev || !obj_emb_dev || !obj_traj_dev || !refine_pose_out_dev)
     return fail(TAMF_ERR_INVALID, "null argument");
-  if (B < 1 || B > c->maxB) return fail(TAMF_ERR_INVALID, "B = " + std::to_string(B) + " outside [1, max_batch = " + std::to_string(c->maxB) + "]");
-  if (T < 1 || T > c->maxT) return fail(TAMF_ERR_INVALID, "T = " + std::to_string(T) + " outside [1, max_frames = " + std::to_string(c->maxT) + "]");
-  if (nobj < 1 || nobj > 4096) return fail(TAMF_ERR_INVALID, range("nobj", nobj, 1, 4096));
-  if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(TAMF_ERR_INVALID, "dropout_p must be in [0, 1)");
-  if (obj_num_host)
-    for (int b = 0; b < B; ++b)
-      if (obj_num_host[b] < 1 || obj_num_host[b] > nobj)
-        return fail(TAMF_ERR_INVALID, "obj_num[" + std::to_string(b) + "] = " + std::to_string(obj_num_host[b]) + " outside [1, nobj = " + std::to_string(nobj) + "]");
-  for (const auto* kv : c->order)  // every tensor has to be there before anything is launched
-    if (!kv->second.p) return fail(TAMF_ERR_MISSING, "missing binding '" + kv->first + "'");
+  if (int rc = check_call(c, B, T, nobj, dropout_p, obj_num_host)) return rc;
   c->have_forward = false;
-  hipError_t e = hipSetDevice(c->device);
-  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
   hipStream_t st = (hipStream_t)stream;
-  if (obj_num_host) e = hipMemcpyAsync(c->cnt, obj_num_host, B * sizeof(int), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && clip_id_host) e = hipMemcpyAsync(c->clip, clip_id_host, B * sizeof(long long), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+  if (int rc = stage_call(c, B, obj_num_host, clip_id_host, st)) return rc;
 
   c->B = B, c->T = T;
   c->io = Batch{sample_pose_dev, h2o_dist_dev, shape_dev, obj_emb_dev, obj_traj_dev, hand_side_dev, obj_num_host ? c->cnt : nullptr, refine_pose_out_dev, nobj};
@@ -558,10 +452,8 @@ int tamf_refinetrain_forward(tamf_refinetrain_ctx* c, int32_t B, int32_t T, int3
 int tamf_refinetrain_backward(tamf_refinetrain_ctx* c, const float* grad_refine_pose_dev, void* stream) {
   if (!c || !grad_refine_pose_dev) return fail(TAMF_ERR_INVALID, "null argument");
   if (!c->have_forward) return fail(TAMF_ERR_STATE, "tamf_refinetrain_backward needs a preceding tamf_refinetrain_forward on this context (a forward serves one backward)");
-  for (const auto* kv : c->order)
-    if (!kv->second.p) return fail(TAMF_ERR_MISSING, "missing binding '" + kv->first + "'");
-  hipError_t e = hipSetDevice(c->device);
-  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+  if (int rc = c->tab.require_bound()) return rc;
+  if (int rc = use_device(c)) return rc;
   c->have_forward = false;
   Step s = make_step(c, (hipStream_t)stream);
   s.backward_head(grad_refine_pose_dev);
@@ -602,15 +494,7 @@ int tamf_refinetrain_get_profile(tamf_refinetrain_ctx* c, char* out, int64_t siz
 
 int tamf_refinetrain_dropout_mask(uint64_t seed, uint32_t step, int64_t clip_id, int32_t site, int32_t rows, int32_t cols, float p,
                                   uint8_t* out_dev, void* stream) {
-  if (!out_dev) return fail(TAMF_ERR_INVALID, "null argument");
-  if (rows < 1 || cols < 1 || (long)rows * cols > 0xFFFFFFFFL) return fail(TAMF_ERR_INVALID, "rows * cols must be in [1, 2^32)");
-  if (site < 0) return fail(TAMF_ERR_INVALID, "site must be >= 0");
-  if (!(p >= 0.f && p < 1.f)) return fail(TAMF_ERR_INVALID, "p must be in [0, 1)");
-  Step s;
-  s.st = (hipStream_t)stream;
-  const long n = (long)rows * cols;
-  s.launch(dropout_mask_kernel, blocks(n, 256), 256, 0, make_drop(seed, step, p, nullptr), site, (unsigned long long)clip_id, n, out_dev);
-  return s.status();
+  return dropout_mask(seed, step, clip_id, site, rows, cols, p, out_dev, stream);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@ that description:
   REFINETRAIN csrc/tamf_refinetrain.hip -> libtamf_refinetrain.so (include/tamf_refinetrain.h: the SegmentRefineModel training step - forward, backward)
 POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
 score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
+ENCTRAIN and REFINETRAIN share tamf_train_host.h (the table of bound tensors, the context base, the call checks, the launcher).
 Every library has its own sources, stamp and lock: building or loading one never touches another."""
 from __future__ import annotations
 

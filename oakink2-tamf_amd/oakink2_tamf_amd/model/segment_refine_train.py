@@ -18,52 +18,30 @@ keep-mask the step uses at one site.
 from __future__ import annotations
 
 import ctypes
-from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import c_char_p, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 from typing import Dict, Mapping, Optional, Sequence
 
 import numpy as np
 import torch
 
 from .. import _lib
-from ..hip_backend import TamfError, _Arch, _dev_f32, _stream_ptr, hand_side_code, obj_num_vector, require_gpu
+from ..hip_backend import _Arch, _dev_f32, _stream_ptr, hand_side_code, obj_num_vector
+from . import _train_step
+from ._train_step import TrainStep, clip_id_vector
 
 BUFFERS = ("hand_side_process.rh_embed", "hand_side_process.lh_embed", "sequence_pos_encoder.pe")
-
-_typed = set()  # library objects whose argtypes are set
+PREFIX = "tamf_refinetrain_"
 
 
 def lib() -> ctypes.CDLL:
-    L = _lib.load_refinetrain()
-    if id(L) not in _typed:
-        L.tamf_refinetrain_last_error.restype = c_char_p
-        L.tamf_refinetrain_last_error.argtypes = []
-        L.tamf_refinetrain_create.argtypes = [POINTER(_Arch), c_int32, c_int32, c_int32, POINTER(c_void_p)]
-        L.tamf_refinetrain_destroy.argtypes = [c_void_p]
-        L.tamf_refinetrain_destroy.restype = None
-        L.tamf_refinetrain_bind.argtypes = [c_void_p, c_char_p, c_void_p, c_void_p, POINTER(c_int64), c_int32]
-        L.tamf_refinetrain_forward.argtypes = [c_void_p, c_int32, c_int32, c_int32] + [c_void_p] * 8 + [c_float, c_uint64, c_uint32, c_void_p, c_void_p]
-        L.tamf_refinetrain_backward.argtypes = [c_void_p, c_void_p, c_void_p]
-        L.tamf_refinetrain_dropout_mask.argtypes = [c_uint64, c_uint32, c_int64, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p]
-        L.tamf_refinetrain_set_profile.argtypes = [c_void_p, c_int32]
-        L.tamf_refinetrain_get_profile.argtypes = [c_void_p, c_char_p, c_int64]
-        _typed.add(id(L))
-    return L
-
-
-def _check(rc: int) -> None:
-    if rc != 0:
-        msg = lib().tamf_refinetrain_last_error()
-        raise TamfError(f"libtamf_refinetrain error {rc}: {msg.decode() if msg else '?'}")
+    return _train_step.typed_lib(_lib.load_refinetrain, PREFIX, {
+        "forward": [c_void_p, c_int32, c_int32, c_int32] + [c_void_p] * 8 + [c_float, c_uint64, c_uint32, c_void_p, c_void_p],
+        "backward": [c_void_p, c_void_p, c_void_p], "set_profile": [c_void_p, c_int32], "get_profile": [c_void_p, c_char_p, c_int64]})
 
 
 def dropout_mask(seed: int, step: int, clip_id: int, site: int, rows: int, cols: int, p: float, device=None) -> torch.Tensor:
     """the (rows, cols) bool keep-mask of one dropout site of one clip (tamf_refinetrain_dropout_mask)"""
-    dev = require_gpu(device)
-    out = torch.empty(int(rows), int(cols), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib().tamf_refinetrain_dropout_mask(int(seed), int(step), int(clip_id), int(site), int(rows), int(cols), float(p),
-                                                   c_void_p(out.data_ptr()), c_void_p(_stream_ptr(dev))))
-    return out.bool()
+    return _train_step.dropout_mask(lib(), PREFIX, seed, step, clip_id, site, rows, cols, p, device)
 
 
 def check_refine_batch(batch: Mapping, h2o_dist, arch: Mapping[str, int], obj_num=None, clip_ids=None):
@@ -94,12 +72,7 @@ def check_refine_batch(batch: Mapping, h2o_dist, arch: Mapping[str, int], obj_nu
     num_np = obj_num_vector(obj_num, B)
     if num_np is not None and (num_np.min() < 1 or num_np.max() > nobj):
         raise ValueError(f"obj_num must be in [1, nobj = {nobj}], got [{int(num_np.min())}, {int(num_np.max())}]")
-    clip_np = None
-    if clip_ids is not None:
-        clip_np = np.ascontiguousarray(torch.as_tensor(clip_ids).cpu().numpy() if isinstance(clip_ids, torch.Tensor) else clip_ids, dtype=np.int64)
-        if clip_np.shape != (B,):
-            raise ValueError(f"clip_ids must hold one id per clip: shape {clip_np.shape} for B = {B}")
-    return B, T, nobj, side, num_np, clip_np
+    return B, T, nobj, side, num_np, clip_id_vector(clip_ids, B)
 
 
 class PendingForward:
@@ -133,90 +106,24 @@ class _TrunkFunction(torch.autograd.Function):
         return None, None, None, None
 
 
-class SegmentRefineTrainStep:
+class SegmentRefineTrainStep(TrainStep):
     """forward(batch) / loss_and_grads(batch, loss, obj_points) around a SegmentRefineModel on a GPU.  Enables requires_grad on the
     parameters (the hand-side embeddings and the PE table are buffers) and allocates their .grad.  dropout=None takes the model's
     (sequence_pos_encoder was built with it)."""
 
+    LIB, PREFIX, BUFFERS = staticmethod(lib), PREFIX, BUFFERS
+
     def __init__(self, model, max_batch: int, max_frames: int, dropout: Optional[float] = None, seed: int = 0):
-        self.model = model
-        self._h = None
-        self.dropout = float(model.seqTransEncoder.layers[0].dropout.p if dropout is None else dropout)
-        if not 0.0 <= self.dropout < 1.0:
-            raise ValueError(f"dropout must be in [0, 1), got {self.dropout}")
-        self.seed = int(seed)
-        self.max_batch, self.max_frames = int(max_batch), int(max_frames)
-        self.device = require_gpu(next(model.parameters()).device)
+        dropout = float(model.seqTransEncoder.layers[0].dropout.p if dropout is None else dropout)
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f"dropout must be in [0, 1), got {dropout}")
         self.arch = dict(model._arch)
         a = self.arch
         arch = _Arch(a["input_dim"], a["obj_input_dim"], a["hand_shape_dim"], a["obj_embed_dim"], a["latent_dim"], a["ff_size"], a["num_layers"],
                      a["num_heads"], 0, a["h2o_dim"], 1)
-        self._L = lib()
-        h = c_void_p()
-        with torch.cuda.device(self.device):
-            _check(self._L.tamf_refinetrain_create(ctypes.byref(arch), self.max_batch, self.max_frames, self.device.index or 0, ctypes.byref(h)))
-        self._h = h
-        self._bound = {}
         self._pending = None
         self._keep = None
-        try:
-            self.bind()
-        except Exception:
-            self.close()
-            raise
-
-    def bind(self, skip: Sequence[str] = ()) -> None:
-        """(Re)bind every tensor of the module where it lives now.  `skip` leaves names unbound (for the tests of the refusals)."""
-        for name, p in self.model.named_parameters():
-            if not p.is_contiguous() or p.dtype != torch.float32:
-                raise TamfError(f"{name}: parameters must be contiguous float32")
-            p.requires_grad_(True)
-            if p.grad is None or p.grad.shape != p.shape or not p.grad.is_contiguous():
-                p.grad = torch.zeros_like(p)
-            if name not in skip:
-                self._bind_one(name, p.data, p.grad)
-        for name, b in self.model.named_buffers():
-            if name in BUFFERS and name not in skip:
-                self._bind_one(name, b, None)
-
-    def _rebind_moved(self) -> None:
-        """Before every step: a parameter whose .grad is None again (optimizer.zero_grad() sets it to None by default) gets its bound
-        gradient tensor back - the backward overwrites every element anyway; a parameter or gradient that lives elsewhere than at the
-        bind is bound again where it is now.  So the kernels never write into a tensor the optimiser does not see."""
-        for name, p in self.model.named_parameters():
-            t, g = self._bound.get(name, (None, None))
-            if t is None:
-                continue  # (left unbound on purpose: the step reports it)
-            if p.grad is None and g is not None and g.shape == p.shape and g.device == p.device:
-                p.requires_grad_(True)
-                p.grad = g
-            if p.grad is None or p.grad.dtype != torch.float32 or not p.grad.is_contiguous() or p.grad.shape != p.shape:
-                p.requires_grad_(True)
-                p.grad = torch.zeros_like(p)
-            if p.data_ptr() != t.data_ptr() or p.grad.data_ptr() != g.data_ptr():
-                if not p.is_contiguous() or p.dtype != torch.float32:
-                    raise TamfError(f"{name}: parameters must be contiguous float32")
-                self._bind_one(name, p.data, p.grad)
-        for name, b in self.model.named_buffers():
-            if name in self._bound and b.data_ptr() != self._bound[name][0].data_ptr():
-                self._bind_one(name, b, None)
-
-    def _bind_one(self, name: str, t: torch.Tensor, g: Optional[torch.Tensor]) -> None:
-        shape = (c_int64 * t.dim())(*t.shape)
-        _check(self._L.tamf_refinetrain_bind(self._h, name.encode(), c_void_p(t.data_ptr()), c_void_p(g.data_ptr() if g is not None else 0), shape, t.dim()))
-        self._bound[name] = (t, g)
-
-    def close(self) -> None:
-        if self._h is not None and self._h.value:
-            torch.cuda.synchronize(self.device)
-            self._L.tamf_refinetrain_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(model, arch, max_batch, max_frames, dropout, seed)
 
     def dropout_mask(self, step: int, clip_id: int, site: int, rows: int, cols: int) -> torch.Tensor:
         """the keep-mask this step object uses (its seed and dropout) at one site of one clip"""
@@ -239,8 +146,7 @@ class SegmentRefineTrainStep:
         gradient).  obj_num: per-clip object counts (None: the mean over all nobj padded rows, the reference's forward); clip_ids: the
         keys of the dropout masks (None: the position in the batch).  -> refine_pose_repr (B, T, input_dim), carrying autograd to
         every parameter's .grad; sample_pose_repr is data and gets no gradient."""
-        if self._h is None:
-            raise TamfError("the training step is closed")
+        self._require_open()
         if self._pending is not None and self._pending.open:
             raise RuntimeError("SegmentRefineTrainStep: the previous forward has had no backward yet and a second forward would replace its "
                                "activations; run its backward first, or drop it with discard_forward()")
@@ -255,11 +161,11 @@ class SegmentRefineTrainStep:
         out = torch.empty(B, T, self.arch["input_dim"], dtype=torch.float32, device=dev)
         null = c_void_p(0)
         with torch.cuda.device(dev):
-            _check(self._L.tamf_refinetrain_forward(
-                self._h, B, T, nobj, num_np.ctypes.data_as(c_void_p) if num_np is not None else null, c_void_p(x.data_ptr()),
+            self._call(
+                "forward", self._h, B, T, nobj, num_np.ctypes.data_as(c_void_p) if num_np is not None else null, c_void_p(x.data_ptr()),
                 c_void_p(hd.data_ptr()), c_void_p(sh.data_ptr()), c_void_p(side_d.data_ptr()), c_void_p(oe.data_ptr()), c_void_p(ot.data_ptr()),
                 clip_np.ctypes.data_as(c_void_p) if clip_np is not None else null, self.dropout, self.seed, int(step),
-                c_void_p(out.data_ptr()), c_void_p(_stream_ptr(dev))))
+                c_void_p(out.data_ptr()), c_void_p(_stream_ptr(dev)))
         self._keep = [x, hd, sh, oe, ot, side_d]  # (the backward reads sample_pose_repr and h2o_dist again)
         self._pending = PendingForward()
         anchor = next(self.model.parameters())
@@ -267,12 +173,12 @@ class SegmentRefineTrainStep:
 
     def profile(self, on: bool) -> None:
         """measurement only: bracket every kernel launch of the following calls with events (tamf_refinetrain_set_profile)"""
-        _check(self._L.tamf_refinetrain_set_profile(self._h, int(bool(on))))
+        self._call("set_profile", self._h, int(bool(on)))
 
     def read_profile(self) -> Dict[str, tuple]:
         """{kind of kernel: (launches, milliseconds)} since the last read (tamf_refinetrain_get_profile); waits for the device"""
         buf = ctypes.create_string_buffer(1 << 16)
-        _check(self._L.tamf_refinetrain_get_profile(self._h, buf, len(buf)))
+        self._call("get_profile", self._h, buf, len(buf))
         rows = [ln.split("\t") for ln in buf.value.decode().splitlines()]
         return {r[0]: (int(r[1]), float(r[2])) for r in rows}
 
@@ -283,12 +189,11 @@ class SegmentRefineTrainStep:
 
     def run_backward(self, grad: torch.Tensor) -> None:
         """tamf_refinetrain_backward: the .grad of every parameter from d loss / d refine_pose_repr (called by autograd)"""
-        if self._h is None:
-            raise TamfError("the training step is closed")
+        self._require_open()
         g = _dev_f32(grad, self.device)
         self._rebind_moved()
         with torch.cuda.device(self.device):
-            _check(self._L.tamf_refinetrain_backward(self._h, c_void_p(g.data_ptr()), c_void_p(_stream_ptr(self.device))))
+            self._call("backward", self._h, c_void_p(g.data_ptr()), c_void_p(_stream_ptr(self.device)))
         self._keep = (self._keep or []) + [g]
 
     def loss_and_grads(self, batch: Mapping, loss, obj_points: torch.Tensor, obj_num: Optional[Sequence[int]] = None,

@@ -95,7 +95,7 @@ def test_create_and_mask_refusals_through_ctypes():
 
 def test_each_key_is_written_once():
     """every key stem of the encoder's state dict - outside the layers, and of one layer - occurs exactly once in the text of
-    csrc/tamf_enctrain.hip: where the tensor is declared"""
+    csrc/tamf_enctrain.hip together with csrc/tamf_train_host.h (the layers' declarations): where the tensor is declared"""
     from encoder_restatement import ARCH_ENCODER, seeded_state_dict
 
     def stem(k):
@@ -107,8 +107,10 @@ def test_each_key_is_written_once():
     per_layer = sorted({stem(k[len(layer):]) for k in keys if k.startswith(layer)})
     assert len(outside) == 13 and len(per_layer) == 7, (outside, per_layer)  # (norm1 and norm2 are two of the seven)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, "oakink2-tamf_amd", "csrc", "tamf_enctrain.hip")) as f:
-        text = f.read()
+    text = ""
+    for name in ("tamf_enctrain.hip", "tamf_train_host.h"):
+        with open(os.path.join(root, "oakink2-tamf_amd", "csrc", name)) as f:
+            text += f.read()
     for s in outside + per_layer:  # (as a whole word: input_process.poseEmbedding is also the tail of obj_input_process.poseEmbedding)
         n = len(re.findall(r"(?<![A-Za-z0-9_.])" + re.escape(s) + r"(?![A-Za-z0-9_])", text))
         assert n == 1, (s, n)

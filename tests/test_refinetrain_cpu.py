@@ -175,6 +175,73 @@ def test_refusal_second_backward_and_second_forward():
     ts._h = None  # (nothing to destroy)
 
 
+TAMF_ERR_INVALID = -1
+HEADS_MSG = "the head dimension must be 64: latent_dim = 64 * num_heads, got latent_dim %d with %d heads"
+FF_MSG = "ff_size must be a multiple of 16 in [16, 4096], got %d"
+
+
+def test_create_and_mask_refusals_through_ctypes():
+    """status and last_error text of every refusal of tamf_refinetrain_create and tamf_refinetrain_dropout_mask that returns before
+    the first device call; *out, a sentinel before the call, is NULL after every refused create that was given both pointers"""
+    import ctypes
+
+    from oakink2_tamf_amd.hip_backend import _Arch
+    from oakink2_tamf_amd.model import segment_refine_train as srt
+
+    lib = srt.lib()
+    good = R.arch_dict(R.ARCH_L1)  # (latent_dim 64, one head, ff_size 16, one layer)
+
+    def create(arch=None, max_batch=2, max_frames=7, null=None):
+        a = dict(good, **(arch or {}))
+        st = _Arch(*[a[k] for k in R.ARCH_NAMES[:8]], 0, a["h2o_dim"], 1)
+        out = ctypes.c_void_p(None if null == "arch" else 0x5A5A5A5A)  # (the null check comes before *out is written)
+        rc = lib.tamf_refinetrain_create(None if null == "arch" else ctypes.byref(st), max_batch, max_frames, 0, None if null == "out" else ctypes.byref(out))
+        return rc, lib.tamf_refinetrain_last_error().decode(), out.value
+
+    cases = [(dict(null="arch"), "null argument"), (dict(null="out"), "null argument"),
+             (dict(arch=dict(num_heads=9, latent_dim=576)), "num_heads = 9 outside [1, 8]"), (dict(arch=dict(num_heads=0)), "num_heads = 0 outside [1, 8]"),
+             (dict(arch=dict(latent_dim=128)), HEADS_MSG % (128, 1)), (dict(arch=dict(ff_size=24)), FF_MSG % 24), (dict(arch=dict(ff_size=4112)), FF_MSG % 4112),
+             (dict(arch=dict(num_layers=0)), "num_layers = 0 outside [1, 64]"), (dict(arch=dict(num_layers=65)), "num_layers = 65 outside [1, 64]")]
+    cases += [(dict(arch={k: v}), f"{k} = {v} outside [1, 4096]")
+              for k in ("input_dim", "obj_input_dim", "hand_shape_dim", "obj_embed_dim", "h2o_dim") for v in (0, 4097)]
+    cases += [(dict(max_frames=1022), "max_frames = 1022 outside [1, 1021]"), (dict(max_frames=0), "max_frames = 0 outside [1, 1021]"),
+              (dict(max_batch=0), "max_batch = 0 outside [1, 65535]"), (dict(max_batch=65536), "max_batch = 65536 outside [1, 65535]")]
+    for kw, text in cases:
+        rc, msg, out = create(**kw)
+        assert (rc, msg) == (TAMF_ERR_INVALID, text), (kw, rc, msg)
+        if kw.get("null") != "out":
+            assert out is None, (kw, out)  # *out == NULL
+
+    buf = (ctypes.c_uint8 * 64)()  # never written: the arguments are checked first
+    ok = dict(site=0, rows=4, cols=4, p=0.5, out=ctypes.addressof(buf))
+    for kw, text in ((dict(out=None), "null argument"), (dict(rows=0), "rows * cols must be in [1, 2^32)"), (dict(site=-1), "site must be >= 0"),
+                     (dict(p=1.0), "p must be in [0, 1)"), (dict(p=float("nan")), "p must be in [0, 1)")):
+        a = dict(ok, **kw)
+        rc = lib.tamf_refinetrain_dropout_mask(3, 1, 2, a["site"], a["rows"], a["cols"], a["p"], a["out"], None)
+        assert (rc, lib.tamf_refinetrain_last_error().decode()) == (TAMF_ERR_INVALID, text), (kw, rc)
+    assert not any(buf)
+
+
+def test_each_key_is_written_once():
+    """every key stem of the refiner's state dict - outside the layers, and of one layer - occurs exactly once in the text of
+    csrc/tamf_refinetrain.hip together with csrc/tamf_train_host.h (the layers' declarations): where the tensor is declared"""
+    def stem(k):
+        return re.sub(r"\.(weight|bias)$", "", k)
+
+    layer = "seqTransEncoder.layers.0."
+    keys = list(R.seeded_state_dict(R.ARCH_TINY, 0))
+    outside = sorted({stem(k) for k in keys if not k.startswith("seqTransEncoder.")})
+    per_layer = sorted({stem(k[len(layer):]) for k in keys if k.startswith(layer)})
+    assert len(outside) == 11 and len(per_layer) == 7, (outside, per_layer)  # (norm1 and norm2 are two of the seven)
+    text = ""
+    for name in ("tamf_refinetrain.hip", "tamf_train_host.h"):
+        with open(os.path.join(HERE, "..", "oakink2-tamf_amd", "csrc", name)) as f:
+            text += f.read()
+    for s in outside + per_layer:  # (as a whole word: input_process.poseEmbedding is also the tail of obj_input_process.poseEmbedding)
+        n = len(re.findall(r"(?<![A-Za-z0-9_.])" + re.escape(s) + r"(?![A-Za-z0-9_])", text))
+        assert n == 1, (s, n)
+
+
 # ---- the library's description ----
 def test_lib_description():
     from oakink2_tamf_amd import _lib
@@ -189,7 +256,9 @@ def test_lib_description():
     (out,) = lib.outputs
     assert out.file == "libtamf_refinetrain.so" and sorted(out.exports) == sorted(set(declared)) and len(declared) == len(set(declared))
     assert lib.sources == _lib._include_closure("tamf_refinetrain.hip")
-    assert {"tamf_refinetrain.hip", "tamf_trunk_grad.h", "tamf_dropout.h", "tamf_f32_tower.h", "tamf_device.h", "tamf_weights.h"} <= set(lib.sources)
-    assert "tamf_dropout.h" in _lib.ENCTRAIN.sources  # the shared dropout scheme
+    assert {"tamf_refinetrain.hip", "tamf_trunk_grad.h", "tamf_dropout.h", "tamf_f32_tower.h", "tamf_device.h", "tamf_weights.h",
+            "tamf_train_host.h"} <= set(lib.sources)
+    assert {"tamf_dropout.h", "tamf_train_host.h"} <= set(_lib.ENCTRAIN.sources)  # the shared dropout scheme and host code
+    assert [l for l in every if "tamf_train_host.h" in l.sources] == [_lib.ENCTRAIN, lib]  # of the two training steps alone
     assert not set(_lib.EXPORTS) & set(out.exports)  # the sampler library gains no export
     assert callable(_lib.load_refinetrain)

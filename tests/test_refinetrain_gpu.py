@@ -289,6 +289,33 @@ def test_sgd_run_follows_the_oracle_curve():
     ts.close()
 
 
+def test_zero_grad_between_steps_keeps_training():
+    """optimizer.zero_grad() sets .grad to None by default: the next forward + backward has to write gradients the optimiser sees"""
+    import torch
+
+    arch = R.ARCH_L1
+    sd, inp, _, G = _sweep_case(arch, 2, 7, False, 8000)
+    m, ts = _step(arch, sd, 2, 7)
+    opt = torch.optim.SGD(m.parameters(), lr=1e-2)
+    batch, g = _batch(inp), torch.from_numpy(G).to("cuda:0")
+    ts.forward(batch).backward(g)
+    first = {k: v.grad.clone() for k, v in m.named_parameters()}
+    opt.zero_grad()
+    assert all(v.grad is None for v in m.parameters())
+    before = {k: v.detach().clone() for k, v in m.named_parameters()}
+    ts.forward(batch).backward(g)
+    for k, v in m.named_parameters():
+        assert v.grad is not None and torch.equal(v.grad, first[k]), k
+    opt.step()
+    assert all(not torch.equal(v.detach(), before[k]) for k, v in m.named_parameters())
+    for v in m.parameters():  # a gradient tensor assigned by the caller is bound where it is
+        v.grad = torch.full_like(v, float("nan"))
+    ts.forward(batch).backward(g)
+    torch.cuda.synchronize()
+    assert all(torch.isfinite(v.grad).all() for v in m.parameters())
+    ts.close()
+
+
 def test_refusals():
     """each limit, backward before forward, an unbound tensor: the status, the message, nothing launched, and a following valid call works"""
     import torch
