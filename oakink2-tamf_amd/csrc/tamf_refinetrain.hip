@@ -1,23 +1,20 @@
 // libtamf_refinetrain.so (include/tamf_refinetrain.h): the host side of the SegmentRefineModel training step - the declared tensors,
 // the workspace and the launch sequences of the kernels of tamf_trunk_grad.h, on the host code of tamf_train_host.h (the table, the
-// context base, the call checks, the launcher).  Host conventions of tamf_weights.h: an int status, a thread-local last-error string,
-// nothing thrown across the ABI.
+// context base, the call checks, the launcher) and tamf_trunk_host.h (the layer stack, shared with libtamf_mdmtrain.so).  Host
+// conventions of tamf_weights.h: an int status, a thread-local last-error string, nothing thrown across the ABI.
 //
-// The layer stack (forward_layer / backward_layer) sees token rows [B][S][d] and nothing of the model around it; the refiner is its
-// input stage (3 prefix rows, frames merged from pose | object trajectory | hand->object distance) and its head (x_in + poseFinal).
+// The layer stack (TrunkStep::forward_layer / backward_layer) sees token rows [B][S][d] and nothing of the model around it; the refiner
+// is its input stage (3 prefix rows, frames merged from pose | object trajectory | hand->object distance) and its head (x_in + poseFinal).
 //
 // Row counts of the workspace structs below: R = B (T + 3) token rows, BT = B T frame rows; the context carves them for (max_batch,
 // max_frames), a call addresses them with its own B and T.
-#include "tamf_train_host.h"
-
-#include <tuple>
+#include "tamf_trunk_host.h"
 
 #include "../../include/tamf_refinetrain.h"
-#include "tamf_trunk_grad.h"
 
 namespace {
 
-constexpr int MAX_SPLIT = 64, SPLIT_ROWS = 256, PREFIX = 3, MAX_S = 1024;
+constexpr int PREFIX = 3;
 
 struct Dims {
   long B, BT, R;
@@ -51,25 +48,15 @@ HeadWs carve_head(Carver& cv, const Dims& n) {
   x.outpre = cv.take(n.BT * n.F);         // [BT][F]  x_in + poseFinal(...) before nan_to_num
   return x;
 }
-struct GradWs {
-  long dx, dz, dym, tt, dx1, datt, dqkv, dh, delta, dpre, dzin, dcat, dout, slab;
+struct GradWs {  // the gradients of the refiner's own buffers, between the layer stack's (TrunkGrads) and the slab
+  long dpre, dzin, dcat, dout;
 };
-GradWs carve_grads(Carver& cv, const Dims& n, long slab_nk) {
+GradWs carve_grads(Carver& cv, const Dims& n) {
   GradWs x;
-  x.dx = cv.take(n.R * n.D);              // [R][d] each: the gradient of a layer's output / input,
-  x.dz = cv.take(n.R * n.D);              //   of a LayerNorm's input,
-  x.dym = cv.take(n.R * n.D);             //   of the linear output under that LayerNorm's residual dropout,
-  x.tt = cv.take(n.R * n.D);              //   dy * xhat (the gain gradient before the column sum),
-  x.dx1 = cv.take(n.R * n.D);             //   of LayerNorm 1's output,
-  x.datt = cv.take(n.R * n.D);            //   of the attention output
-  x.dqkv = cv.take(n.R * 3 * n.D);        // [R][3 d]
-  x.dh = cv.take(n.R * n.ff);             // [R][ff]
-  x.delta = cv.take(n.R * n.H);           // [B][H][S]  sum_k P dP of every query
   x.dpre = cv.take(n.R * n.D);            // [R][d]     of InputWs::pre,
   x.dzin = cv.take(n.BT * n.D);           // [BT][d]    zpre,
   x.dcat = cv.take(n.BT * 3 * n.D);       // [BT][3 d]  cat
   x.dout = cv.take(n.BT * n.F);           // [BT][F]    of HeadWs::outpre
-  x.slab = cv.take(slab_nk * MAX_SPLIT);  // [<= 64 splits][N][K + 1] weight-gradient partial sums of the largest linear map
   return x;
 }
 
@@ -92,13 +79,12 @@ struct tamf_refinetrain_ctx : TrainCtx {
   InputWs in;
   std::vector<LayerWs> lw;
   HeadWs hw;
+  TrunkGrads tg;
   GradWs g;
   // the forward whose activations the workspace holds
   bool have_forward = false;
   int B = 0, T = 0;
-  // tamf_refinetrain_set_profile: a pair of events around every launch, read and freed by tamf_refinetrain_get_profile
-  bool profile = false;
-  std::vector<std::tuple<const char*, hipEvent_t, hipEvent_t>> marks;
+  Profile profile;  // tamf_refinetrain_set_profile / tamf_refinetrain_get_profile
   Batch io{};
   Drop drop{};
 };
@@ -123,20 +109,6 @@ void declare_model(tamf_refinetrain_ctx* c) {
   for (int l = 0; l < a.num_layers; ++l) c->lp.push_back(t.declare_layer(l, D, a.ff_size));
   c->head = t.declare_linear("output_process.poseFinal", a.input_dim, D);
 }
-
-// the epilogue of a tg_lin_kernel launch: a TgMode with the operands that mode reads
-struct Epi {
-  int mode = TG_LIN;
-  float* C2 = nullptr;
-  const float* R = nullptr;
-  int site = 0;
-};
-Epi silu(float* pre) { return {TG_SILU, pre}; }
-Epi gelu_drop(float* pre, int site) { return {TG_GELU_DROP, pre, nullptr, site}; }
-Epi drop_res(const float* res, int site) { return {TG_DROP_RES, nullptr, res, site}; }
-Epi bwd_silu(const float* pre) { return {TG_BWD_SILU, nullptr, pre}; }
-Epi bwd_gelu_drop(const float* pre, int site) { return {TG_BWD_GELU_DROP, nullptr, pre, site}; }
-Epi bwd_res(const float* res) { return {TG_BWD_RES, nullptr, res}; }
 
 // ---- the input stage: means, the hand-side row, x0 = drop(nan_to_num(pre) + PE), the output mask ----
 struct PrepArgs {
@@ -178,139 +150,16 @@ __global__ void prep_kernel(const PrepArgs a) {
     a.pre[(long)b * S * a.D + c] = (a.side[b] ? a.lh : a.rh)[c];
   }
 }
-// X0 = drop(nan_to_num(pre) + PE) over [B][S][d]; its backward: dpre = dX0 * drop factor * isfinite(pre)
-__global__ void assemble_kernel(const float* pre, const float* pe, float* x0, const float* dx0, float* dpre, int B, int S, int D, Drop d) {
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= (long)B * S * D) return;
-  const int b = (int)(e / ((long)S * D));
-  const uint32_t el = (uint32_t)(e % ((long)S * D));
-  const float f = drop_factor(d, 0, b, el), v = pre[e];
-  if (x0) x0[e] = (nan_to_num(v) + pe[el]) * f;
-  else dpre[e] = (v - v == 0.f) ? dx0[e] * f : 0.f;  // (v - v: 0 for a finite v, NaN otherwise)
-}
-// dpre = isfinite(pre) ? dout : 0 (the output's nan_to_num)
-__global__ void finite_mask_kernel(const float* pre, const float* dout, float* dpre, long n) {
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  const float v = pre[e];
-  dpre[e] = (v - v == 0.f) ? dout[e] : 0.f;
-}
-
-struct Step : StepRows {
+struct Step : TrunkStep<Step> {
+  static constexpr int MAX_HD = 64;  // (tamf_refinetrain_create refuses another head dimension)
   tamf_refinetrain_ctx* c = nullptr;
   Dims n{};
   Batch io{};
-  Drop drop{};
-  const char* tag = "other";  // what the next launches are called in the profile
-
-  RowMap tok(long ld) const { return rows(S, ld); }  // every token row, split into (clip, row)
 
   // the shared launch, between a pair of events when the context's profile is on
   template <class K, class... A>
   void launch(K kernel, dim3 grid, int block, size_t lds, A... args) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timed = c->profile && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-    if (timed) (void)hipEventRecord(e0, st);
-    Launcher::launch(kernel, grid, block, lds, args...);
-    if (timed) {
-      (void)hipEventRecord(e1, st);
-      c->marks.emplace_back(tag, e0, e1);
-    }
-  }
-
-  void lin(TgLin a, const Epi& e, bool wt) {
-    a.rm = a.cm;
-    a.mode = e.mode;
-    a.C2 = e.C2;
-    a.R = e.R;
-    a.site = e.site;
-    a.d = drop;
-    const dim3 grid((a.M + TG_T - 1) / TG_T, (a.N + TG_T - 1) / TG_T);
-    tag = wt ? "tg_lin_kernel<dgrad>" : "tg_lin_kernel<fwd>";
-    if (wt) launch(tg_lin_kernel<true>, grid, 256, 0, a);
-    else launch(tg_lin_kernel<false>, grid, 256, 0, a);
-  }
-  // C (M, N) = epilogue(A (M, K) . W^T + b) of a linear map
-  void fwd(const Lin& l, const float* A, RowMap am, float* C, RowMap cm, int M, const Epi& e = {}) {
-    TgLin a{};
-    a.A = A, a.am = am, a.W = l.w->p, a.swn = l.K, a.swk = 1, a.bias = l.b->p, a.C = C, a.cm = cm, a.M = M, a.N = l.N, a.K = l.K;
-    lin(a, e, false);
-  }
-  // the data gradient of the same map: dA (M, K) = epilogue(dY (M, N) . W)
-  void dgrad(const Lin& l, const float* dY, RowMap ym, float* dA, RowMap cm, int M, const Epi& e = {}) {
-    TgLin a{};
-    a.A = dY, a.am = ym, a.W = l.w->p, a.swn = 1, a.swk = l.K, a.C = dA, a.cm = cm, a.M = M, a.N = l.K, a.K = l.N;
-    lin(a, e, true);
-  }
-  // the split of R rows: a function of the row count alone
-  static int splits(int R) { return std::max(1, std::min(MAX_SPLIT, (R + SPLIT_ROWS - 1) / SPLIT_ROWS)); }
-  // its weight and bias gradients from its output gradient Y and its input A over R rows
-  void wgrad(const Lin& l, const float* Y, RowMap ym, const float* A, RowMap am, int R) {
-    const int N = l.N, K = l.K, nsplit = splits(R), chunk = ((R + nsplit - 1) / nsplit + TG_K - 1) / TG_K * TG_K;
-    tag = "tg_wgrad_kernel";
-    launch(tg_wgrad_kernel, dim3((N + TG_T - 1) / TG_T, (K + 1 + TG_T - 1) / TG_T, nsplit), 256, 0, TgWgrad{Y, ym, A, am, w(c->g.slab), R, N, K, chunk});
-    tag = "reduce_kernel";
-    launch(reduce_kernel, blocks((long)N * (K + 1), 256), 256, 0, w(c->g.slab), nsplit, N, K + 1, K, l.w->g, l.b->g);
-  }
-  // the column sums of two [R][d] buffers at once (a LayerNorm's gain and bias gradients), through the two halves of the slab
-  void colsum2(const float* A, const float* Bm, int R, float* outa, float* outb) {
-    const int nsplit = splits(R);
-    float *pa = w(c->g.slab), *pb = pa + (long)MAX_SPLIT * D;
-    tag = "tg_colsum2_kernel + reduce";
-    launch(tg_colsum2_kernel, dim3(nsplit, D / 64), 256, 0, A, Bm, D, R, (R + nsplit - 1) / nsplit, pa, pb);
-    launch(reduce_kernel, blocks(D, 256), 256, 0, pa, nsplit, 1, D, D, outa, nullptr);
-    launch(reduce_kernel, blocks(D, 256), 256, 0, pb, nsplit, 1, D, D, outb, nullptr);
-  }
-  void ln_fwd(const float* X, float* Y, const Lin& norm) {
-    tag = "tg_ln_fwd_kernel";
-    launch(tg_ln_fwd_kernel, blocks(n.R, 4), 256, 0, X, Y, norm.w->p, norm.b->p, (int)n.R, D);
-  }
-  // LayerNorm backward of dy (offsets): dz, dym = dz under the dropout of `site`, the gain and bias gradients
-  void ln_bwd(long dy, long pre, const Lin& norm, int site) {
-    const GradWs& g = c->g;
-    tag = "tg_ln_bwd_kernel";
-    launch(tg_ln_bwd_kernel, blocks(n.R, 4), 256, 0, w(dy), w(pre), norm.w->p, w(g.dz), w(g.dym), w(g.tt), (int)n.R, D, S, site, drop);
-    colsum2(w(g.tt), w(dy), (int)n.R, norm.w->g, norm.b->g);
-  }
-  dim3 attn_grid() const { return dim3((S + 15) / 16, n.H, B); }
-
-  // ---- the layer stack: token rows in, token rows out ----
-  void forward_layer(int l) {
-    const LayerWs& x = c->lw[l];
-    const LayerP& p = c->lp[l];
-    const int site = 1 + 4 * l, R = (int)n.R;
-    fwd(p.inproj, xof(l), flat(D), w(x.qkv), flat(3 * D), R);
-    tag = "tg_attn_fwd_kernel";
-    launch(tg_attn_fwd_kernel, attn_grid(), 64, 0, TgAttn{w(x.qkv), w(x.att), w(x.stat), nullptr, nullptr, nullptr, S, n.H, site, drop});
-    fwd(p.out, w(x.att), flat(D), w(x.x1pre), tok(D), R, drop_res(xof(l), site + 1));
-    ln_fwd(w(x.x1pre), w(x.x1), p.n1);
-    fwd(p.l1, w(x.x1), flat(D), w(x.gel), tok(n.ff), R, gelu_drop(w(x.hpre), site + 2));
-    fwd(p.l2, w(x.gel), flat(n.ff), w(x.x2pre), tok(D), R, drop_res(w(x.x1), site + 3));
-    ln_fwd(w(x.x2pre), xof(l + 1), p.n2);
-  }
-  // g.dx: the gradient of the layer's output on entry, of its input on return
-  void backward_layer(int l) {
-    const LayerWs& x = c->lw[l];
-    const LayerP& p = c->lp[l];
-    const GradWs& g = c->g;
-    const int site = 1 + 4 * l, R = (int)n.R;
-    // LayerNorm 2, the feed-forward block
-    ln_bwd(g.dx, x.x2pre, p.n2, site + 3);
-    wgrad(p.l2, w(g.dym), flat(D), w(x.gel), flat(n.ff), R);
-    dgrad(p.l2, w(g.dym), flat(D), w(g.dh), tok(n.ff), R, bwd_gelu_drop(w(x.hpre), site + 2));
-    wgrad(p.l1, w(g.dh), flat(n.ff), w(x.x1), flat(D), R);
-    dgrad(p.l1, w(g.dh), flat(n.ff), w(g.dx1), flat(D), R, bwd_res(w(g.dz)));
-    // LayerNorm 1, out-projection, attention, in-projection
-    ln_bwd(g.dx1, x.x1pre, p.n1, site + 1);
-    wgrad(p.out, w(g.dym), flat(D), w(x.att), flat(D), R);
-    dgrad(p.out, w(g.dym), flat(D), w(g.datt), flat(D), R);
-    const TgAttn a{w(x.qkv), w(x.att), w(x.stat), w(g.datt), w(g.dqkv), w(g.delta), S, n.H, site, drop};
-    tag = "tg_attn_bwd_q_kernel";
-    launch(tg_attn_bwd_q_kernel, attn_grid(), 64, 0, a);
-    tag = "tg_attn_bwd_kv_kernel";
-    launch(tg_attn_bwd_kv_kernel, attn_grid(), 64, 0, a);
-    wgrad(p.inproj, w(g.dqkv), flat(3 * D), xof(l), flat(D), R);
-    dgrad(p.inproj, w(g.dqkv), flat(3 * D), w(g.dx), flat(D), R, bwd_res(w(g.dz)));
+    c->profile.around(tag, st, [&] { Launcher::launch(kernel, grid, block, lds, args...); });
   }
 
   // ---- the refiner around it ----
@@ -341,14 +190,14 @@ struct Step : StepRows {
     tag = "input stage (elementwise)";
     launch(finite_mask_kernel, blocks(n.BT * n.F, 256), 256, 0, w(c->hw.outpre), gout, w(g.dout), n.BT * n.F);
     wgrad(c->head, w(g.dout), flat(n.F), fr, frames(), (int)n.BT);
-    if (err == hipSuccess) err = hipMemsetAsync(w(g.dx), 0, n.R * D * sizeof(float), st);  // (the prefix rows feed no output row)
-    dgrad(c->head, w(g.dout), flat(n.F), w(g.dx) + PREFIX * D, frames(), (int)n.BT);
+    if (err == hipSuccess) err = hipMemsetAsync(w(tg.dx), 0, n.R * D * sizeof(float), st);  // (the prefix rows feed no output row)
+    dgrad(c->head, w(g.dout), flat(n.F), w(tg.dx) + PREFIX * D, frames(), (int)n.BT);
   }
   void backward_input() {
     const InputWs& x = c->in;
     const GradWs& g = c->g;
     tag = "input stage (elementwise)";
-    launch(assemble_kernel, blocks(n.R * D, 256), 256, 0, w(x.pre), c->pe->p, nullptr, w(g.dx), w(g.dpre), B, S, D, drop);
+    launch(assemble_kernel, blocks(n.R * D, 256), 256, 0, w(x.pre), c->pe->p, nullptr, w(tg.dx), w(g.dpre), B, S, D, drop);
     wgrad(c->shape, w(g.dpre) + 1 * D, one(), w(x.shm), flat(n.sd), B);
     wgrad(c->obj, w(g.dpre) + 2 * D, one(), w(x.oem), flat(n.od), B);
     const float* dfr = w(g.dpre) + PREFIX * D;
@@ -369,6 +218,7 @@ Step make_step(tamf_refinetrain_ctx* c, hipStream_t st) {
   s.ws = c->ws, s.lw = &c->lw, s.xlast = c->hw.xlast;
   s.n = dims(c->arch, c->B, c->T);
   s.B = c->B, s.T = c->T, s.S = c->T + PREFIX, s.D = c->arch.latent_dim;
+  s.lp = &c->lp, s.tg = c->tg, s.R = s.n.R, s.H = s.n.H, s.ff = s.n.ff;
   s.io = c->io;
   s.drop = c->drop;
   return s;
@@ -407,7 +257,9 @@ int tamf_refinetrain_create(const tamf_arch* arch, int32_t max_batch, int32_t ma
   c->in = carve_input(cv, n);
   for (int l = 0; l < arch->num_layers; ++l) c->lw.push_back(carve_layer(cv, n.R, n.D, n.H, n.ff));
   c->hw = carve_head(cv, n);
-  c->g = carve_grads(cv, n, c->tab.slab_nk);
+  c->tg = carve_trunk_grads(cv, n.R, n.D, n.H, n.ff);
+  c->g = carve_grads(cv, n);
+  c->tg.slab = carve_slab(cv, c->tab.slab_nk);
   if (int rc = alloc_buffers(c, cv)) {
     tamf_refinetrain_destroy(c);
     return rc;
@@ -418,7 +270,7 @@ int tamf_refinetrain_create(const tamf_arch* arch, int32_t max_batch, int32_t ma
 
 void tamf_refinetrain_destroy(tamf_refinetrain_ctx* c) {
   if (!c) return;
-  for (auto& m : c->marks) (void)hipEventDestroy(std::get<1>(m)), (void)hipEventDestroy(std::get<2>(m));
+  c->profile.clear();
   free_buffers(c);
   delete c;
 }
@@ -464,32 +316,13 @@ int tamf_refinetrain_backward(tamf_refinetrain_ctx* c, const float* grad_refine_
 
 int tamf_refinetrain_set_profile(tamf_refinetrain_ctx* c, int32_t on) {
   if (!c) return fail(TAMF_ERR_INVALID, "null argument");
-  c->profile = on != 0;
+  c->profile.on = on != 0;
   return 0;
 }
 
 int tamf_refinetrain_get_profile(tamf_refinetrain_ctx* c, char* out, int64_t size) {
   if (!c || !out || size < 1) return fail(TAMF_ERR_INVALID, "null argument");
-  std::map<std::string, std::pair<long, double>> sum;  // name -> (launches, ms)
-  hipError_t e = hipSuccess;
-  for (auto& m : c->marks) {
-    float ms = 0.f;
-    if (e == hipSuccess) e = hipEventSynchronize(std::get<2>(m));
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, std::get<1>(m), std::get<2>(m));
-    (void)hipEventDestroy(std::get<1>(m));
-    (void)hipEventDestroy(std::get<2>(m));
-    auto& s = sum[std::get<0>(m)];
-    s.first += 1;
-    s.second += ms;
-  }
-  c->marks.clear();
-  if (e != hipSuccess) return fail(TAMF_ERR_HIP, std::string("profile events: ") + hipGetErrorString(e));
-  std::string text;
-  for (const auto& kv : sum) text += kv.first + "\t" + std::to_string(kv.second.first) + "\t" + std::to_string(kv.second.second) + "\n";
-  if ((int64_t)text.size() + 1 > size) return fail(TAMF_ERR_INVALID, "the profile needs " + std::to_string(text.size() + 1) + " bytes");
-  std::copy(text.begin(), text.end(), out);
-  out[text.size()] = 0;
-  return 0;
+  return c->profile.report(out, size);
 }
 
 int tamf_refinetrain_dropout_mask(uint64_t seed, uint32_t step, int64_t clip_id, int32_t site, int32_t rows, int32_t cols, float p,

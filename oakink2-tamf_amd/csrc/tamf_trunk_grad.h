@@ -1,14 +1,14 @@
-// Training kernels of a post-LN transformer trunk at head dimension 64 (libtamf_refinetrain.so), fp32 throughout.  Every contraction
-// runs on v_mfma_f32_16x16x4_f32.  Nothing here knows the model around the layer stack: the input stage and the head are launch
-// sequences of the host file over the same kernels.
+// Training kernels of a post-LN transformer trunk at head dimension 64 or 128 (libtamf_refinetrain.so, libtamf_mdmtrain.so), fp32
+// throughout.  Every contraction runs on v_mfma_f32_16x16x4_f32.  Nothing here knows the model around the layer stack: the input
+// stage and the head are launch sequences of the host file over the same kernels.
 //
 //   tg_lin_kernel<WT>  C = epi(A . W^T + bias) over a 64 x 64 tile per workgroup, the contraction in steps of 32 through LDS.  WT = false
 //                      reads W[n][k] (forward); WT = true reads the same W by its other stride, W[k][n] (data gradient).  An output
 //                      element is one accumulator chain over k ascending: its bits do not depend on where its row sits in the batch.
 //   tg_wgrad_kernel    part[s][n][k] = sum over the token rows of split s of dY[r][n] X[r][k], the same tile with the rows as the
 //                      contraction; column k = K is the sum of dY itself (the bias gradient).  reduce_kernel adds the splits in order.
-//   tg_attn_*          one wave per 16 query rows (forward, dQ) or 16 key rows (dK, dV) of a (clip, head).  Scores and dP are
-//                      f32_score_tile products; a 16 x 16 tile of P (or dS) goes through LDS once, from the MFMA's output layout to its
+//   tg_attn_*<HD>      one wave per 16 query rows (forward, dQ) or 16 key rows (dK, dV) of a (clip, head).  Scores and dP are
+//                      tg_score_tile products; a 16 x 16 tile of P (or dS) goes through LDS once, from the MFMA's output layout to its
 //                      A-operand layout, and is contracted against V (K, Q, dO) rows read from global memory.  The probabilities are
 //                      recomputed from the stored row maximum and sum; their dropout is regenerated.
 //   tg_ln_*            LayerNorm of a row by one wave, its backward with the statistics recomputed from the stored input.
@@ -29,7 +29,7 @@
 #include "tamf_dropout.h"
 #include "tamf_f32_tower.h"
 
-constexpr int TG_HD = F32_HD;                            // head dimension
+constexpr int TG_HD = F32_HD;                            // the head dimension of the refiner's configurations (the kernels: 64 or 128)
 constexpr int TG_T = 64, TG_K = 32, TG_LD = TG_K + 4;    // GEMM tile, contraction step, LDS row stride (floats)
 constexpr int TG_PLD = 17;                               // row stride of an attention wave's 16 x 16 LDS tile
 
@@ -42,6 +42,7 @@ enum TgMode {
   TG_BWD_SILU,       // C = v * silu'(R)
   TG_BWD_GELU_DROP,  // C = v * drop factor * gelu'(R)
   TG_BWD_RES,        // C = v + R
+  TG_HEAD,           // C2 = v, C = nan_to_num(v)
 };
 
 // the 32-deep step of a workgroup's 64 x 64 tile: wave (wm, wn) owns the 32 x 32 block at (32 wm, 32 wn) as 2 x 2 MFMA tiles
@@ -149,6 +150,10 @@ __global__ __launch_bounds__(256) void tg_lin_kernel(const TgLin a) {
           case TG_BWD_SILU: o = v * silu_grad(a.R[a.rm.at(m) + n]); break;
           case TG_BWD_GELU_DROP: o = v * drop_factor(a.d, a.site, b, (uint32_t)row * a.N + n) * gelu_grad(a.R[a.rm.at(m) + n]); break;
           case TG_BWD_RES: o = v + a.R[a.rm.at(m) + n]; break;
+          case TG_HEAD:
+            a.C2[co] = v;
+            o = nan_to_num(v);
+            break;
         }
         a.C[co] = o;
       }
@@ -293,7 +298,8 @@ __global__ __launch_bounds__(256) void tg_ln_bwd_kernel(const float* DY, const f
   }
 }
 
-// ---- attention at head dimension 64.  QKV rows are [q(d) | k(d) | v(d)], head h at 64 h; one wave per workgroup ----
+// ---- attention at head dimension HD = 64 or 128.  QKV rows are [q(d) | k(d) | v(d)], head h at HD h; one wave per workgroup.  Lane
+// (r, g) holds the HD / 4 contiguous floats of its row at column (HD / 4) g, as HD / 16 float4 ----
 struct TgAttn {
   const float* qkv;   // [B][S][3 d]
   float* att;         // [B][S][d]    the attention output (forward: written; backward: read for delta)
@@ -311,44 +317,71 @@ TAMF_DEV float tg_row_reduce(float v) {  // over the 16 lanes r of a lane group;
   v = R::op(v, dpp_mov<DPP_ROW_HALF_MIRROR>(v));
   return R::op(v, dpp_mov<DPP_ROW_MIRROR>(v));
 }
+// this lane's HD / 4 floats of a row; zeros for a row that is not there
+template <int HD>
+TAMF_DEV void tg_load_row(float4 (&q4)[HD / 16], bool in, const float* q) {
+  const float4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  const float4* qp = reinterpret_cast<const float4*>(q);
+#pragma unroll
+  for (int j = 0; j < HD / 16; ++j) q4[j] = in ? qp[j] : zero4;
+}
+// a 16 x 16 tile of q . k^T over the HD floats of a head, HD / 4 MFMAs -> element e: row 4g + e of q4's tile against row r of k's
+// (unscaled)
+template <int HD>
+TAMF_DEV f32x4 tg_score_tile(const float4 (&q4)[HD / 16], const float* k, bool in) {
+  float4 k4[HD / 16];
+  tg_load_row<HD>(k4, in, k);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < HD / 16; ++j) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(q4[j].x, k4[j].x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(q4[j].y, k4[j].y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(q4[j].z, k4[j].z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(q4[j].w, k4[j].w, acc, 0, 0, 0);
+  }
+  return acc;
+}
 // acc[jt] += T . X over one 16-row tile: T the wave's 16 x 16 LDS tile (row r of this lane as the A operand), X the rows x0 .. x0 + 15
-// of a [S][ld] buffer at column c0 (64 columns = 4 output tiles), rows >= S contributing nothing
-TAMF_DEV void tg_tile_mma(const float* tile, const float* X, long ld, int x0, int S, int r, int g, f32x4 (&acc)[4]) {
+// of a [S][ld] buffer at column c0 (HD columns = HD / 16 output tiles), rows >= S contributing nothing
+template <int HD>
+TAMF_DEV void tg_tile_mma(const float* tile, const float* X, long ld, int x0, int S, int r, int g, f32x4 (&acc)[HD / 16]) {
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) {
     const int x = x0 + 4 * kk + g;
     const float av = tile[r * TG_PLD + 4 * kk + g];
     const float* xp = X + (long)x * ld + r;
 #pragma unroll
-    for (int jt = 0; jt < 4; ++jt) acc[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, x < S ? xp[16 * jt] : 0.f, acc[jt], 0, 0, 0);
+    for (int jt = 0; jt < HD / 16; ++jt) acc[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, x < S ? xp[16 * jt] : 0.f, acc[jt], 0, 0, 0);
   }
 }
+template <int HD>
 __global__ __launch_bounds__(64) void tg_attn_fwd_kernel(const TgAttn a) {
+  constexpr int NQ = HD / 16, LC = HD / 4;  // float4 per lane, floats per lane
   __shared__ float tile[16 * TG_PLD];
-  const int S = a.S, h = blockIdx.y, b = blockIdx.z, d = a.H * TG_HD, lane = threadIdx.x, r = lane & 15, g = lane >> 4;
+  const int S = a.S, h = blockIdx.y, b = blockIdx.z, d = a.H * HD, lane = threadIdx.x, r = lane & 15, g = lane >> 4;
   const int q0 = blockIdx.x * 16;
   const long ld = 3L * d;
-  const float* base = a.qkv + (long)b * S * ld + h * TG_HD;
-  const float scale = 1.0f / sqrtf((float)TG_HD);
-  float4 q4[4];
-  f32_load_q(q4, q0 + r < S, base + (long)min(q0 + r, S - 1) * ld + 16 * g);
+  const float* base = a.qkv + (long)b * S * ld + h * HD;
+  const float scale = 1.0f / sqrtf((float)HD);
+  float4 q4[NQ];
+  tg_load_row<HD>(q4, q0 + r < S, base + (long)min(q0 + r, S - 1) * ld + LC * g);
   float mx[4], sum[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) mx[e] = -__builtin_inff(), sum[e] = 0.f;
   for (int k0 = 0; k0 < S; k0 += 16) {
     const bool in = k0 + r < S;
-    const f32x4 sc = f32_score_tile(q4, base + d + (long)min(k0 + r, S - 1) * ld + 16 * g, in);
+    const f32x4 sc = tg_score_tile<HD>(q4, base + d + (long)min(k0 + r, S - 1) * ld + LC * g, in);
 #pragma unroll
     for (int e = 0; e < 4; ++e) mx[e] = in ? fmaxf(mx[e], sc[e] * scale) : mx[e];
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) mx[e] = tg_row_reduce<RedMax>(mx[e]);
-  f32x4 o[4];
+  f32x4 o[NQ];
 #pragma unroll
-  for (int jt = 0; jt < 4; ++jt) o[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int jt = 0; jt < NQ; ++jt) o[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int k0 = 0; k0 < S; k0 += 16) {
     const bool in = k0 + r < S;
-    const f32x4 sc = f32_score_tile(q4, base + d + (long)min(k0 + r, S - 1) * ld + 16 * g, in);
+    const f32x4 sc = tg_score_tile<HD>(q4, base + d + (long)min(k0 + r, S - 1) * ld + LC * g, in);
     __syncthreads();  // the previous tile's reads are done
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -358,7 +391,7 @@ __global__ __launch_bounds__(64) void tg_attn_fwd_kernel(const TgAttn a) {
       tile[(4 * g + e) * TG_PLD + r] = p == 0.f ? 0.f : p * drop_factor(a.d, a.site, b, (uint32_t)(h * S + q) * S + k0 + r);
     }
     __syncthreads();
-    tg_tile_mma(tile, base + 2 * d, ld, k0, S, r, g, o);
+    tg_tile_mma<HD>(tile, base + 2 * d, ld, k0, S, r, g, o);
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -367,7 +400,7 @@ __global__ __launch_bounds__(64) void tg_attn_fwd_kernel(const TgAttn a) {
     if (q >= S) continue;
     const float inv = 1.0f / sum[e];
 #pragma unroll
-    for (int jt = 0; jt < 4; ++jt) a.att[((long)b * S + q) * d + h * TG_HD + 16 * jt + r] = o[jt][e] * inv;
+    for (int jt = 0; jt < NQ; ++jt) a.att[((long)b * S + q) * d + h * HD + 16 * jt + r] = o[jt][e] * inv;
     if (r == 0) {
       float* st = a.stat + (((long)b * a.H + h) * S + q) * 2;
       st[0] = mx[e];
@@ -376,22 +409,27 @@ __global__ __launch_bounds__(64) void tg_attn_fwd_kernel(const TgAttn a) {
   }
 }
 // dQ of 16 query rows and their delta
+template <int HD>
 __global__ __launch_bounds__(64) void tg_attn_bwd_q_kernel(const TgAttn a) {
+  constexpr int NQ = HD / 16, LC = HD / 4;
   __shared__ float tile[16 * TG_PLD], dl[16];
-  const int S = a.S, h = blockIdx.y, b = blockIdx.z, d = a.H * TG_HD, lane = threadIdx.x, r = lane & 15, g = lane >> 4;
+  const int S = a.S, h = blockIdx.y, b = blockIdx.z, d = a.H * HD, lane = threadIdx.x, r = lane & 15, g = lane >> 4;
   const int q0 = blockIdx.x * 16;
   const long ld = 3L * d;
-  const float* base = a.qkv + (long)b * S * ld + h * TG_HD;
-  const float scale = 1.0f / sqrtf((float)TG_HD);
+  const float* base = a.qkv + (long)b * S * ld + h * HD;
+  const float scale = 1.0f / sqrtf((float)HD);
   const bool qin = q0 + r < S;
   const long qr = (long)b * S + min(q0 + r, S - 1);
-  float4 q4[4], do4[4], o4[4];
-  f32_load_q(q4, qin, base + (qr - (long)b * S) * ld + 16 * g);
-  f32_load_q(do4, qin, a.datt + qr * d + h * TG_HD + 16 * g);
-  f32_load_q(o4, qin, a.att + qr * d + h * TG_HD + 16 * g);
+  float4 q4[NQ], do4[NQ];
   float dp = 0.f;
+  {
+    float4 o4[NQ];  // (only for delta)
+    tg_load_row<HD>(q4, qin, base + (qr - (long)b * S) * ld + LC * g);
+    tg_load_row<HD>(do4, qin, a.datt + qr * d + h * HD + LC * g);
+    tg_load_row<HD>(o4, qin, a.att + qr * d + h * HD + LC * g);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) dp += do4[j].x * o4[j].x + do4[j].y * o4[j].y + do4[j].z * o4[j].z + do4[j].w * o4[j].w;
+    for (int j = 0; j < NQ; ++j) dp += do4[j].x * o4[j].x + do4[j].y * o4[j].y + do4[j].z * o4[j].z + do4[j].w * o4[j].w;
+  }
   dp = groups_reduce<RedSum>(dp);  // query q0 + r
   if (g == 0) {
     dl[r] = dp;
@@ -407,14 +445,14 @@ __global__ __launch_bounds__(64) void tg_attn_bwd_q_kernel(const TgAttn a) {
     inv[e] = 1.0f / st[1];
     del[e] = dl[4 * g + e];
   }
-  f32x4 acc[4];
+  f32x4 acc[NQ];
 #pragma unroll
-  for (int jt = 0; jt < 4; ++jt) acc[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int jt = 0; jt < NQ; ++jt) acc[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int k0 = 0; k0 < S; k0 += 16) {
     const bool in = k0 + r < S;
-    const long kr = (long)min(k0 + r, S - 1) * ld + 16 * g;
-    const f32x4 sc = f32_score_tile(q4, base + d + kr, in);
-    const f32x4 dpv = f32_score_tile(do4, base + 2 * d + kr, in);
+    const long kr = (long)min(k0 + r, S - 1) * ld + LC * g;
+    const f32x4 sc = tg_score_tile<HD>(q4, base + d + kr, in);
+    const f32x4 dpv = tg_score_tile<HD>(do4, base + 2 * d + kr, in);
     __syncthreads();
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -427,39 +465,41 @@ __global__ __launch_bounds__(64) void tg_attn_bwd_q_kernel(const TgAttn a) {
       tile[(4 * g + e) * TG_PLD + r] = ds;
     }
     __syncthreads();
-    tg_tile_mma(tile, base + d, ld, k0, S, r, g, acc);
+    tg_tile_mma<HD>(tile, base + d, ld, k0, S, r, g, acc);
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int q = q0 + 4 * g + e;
     if (q >= S) continue;
 #pragma unroll
-    for (int jt = 0; jt < 4; ++jt) a.dqkv[((long)b * S + q) * ld + h * TG_HD + 16 * jt + r] = acc[jt][e] * scale;
+    for (int jt = 0; jt < NQ; ++jt) a.dqkv[((long)b * S + q) * ld + h * HD + 16 * jt + r] = acc[jt][e] * scale;
   }
 }
 // dK and dV of 16 key rows: the query tiles in ascending order
+template <int HD>
 __global__ __launch_bounds__(64) void tg_attn_bwd_kv_kernel(const TgAttn a) {
+  constexpr int NQ = HD / 16, LC = HD / 4;
   __shared__ float tp[16 * TG_PLD], td[16 * TG_PLD];
-  const int S = a.S, h = blockIdx.y, b = blockIdx.z, d = a.H * TG_HD, lane = threadIdx.x, r = lane & 15, g = lane >> 4;
+  const int S = a.S, h = blockIdx.y, b = blockIdx.z, d = a.H * HD, lane = threadIdx.x, r = lane & 15, g = lane >> 4;
   const int k0 = blockIdx.x * 16;
   const long ld = 3L * d;
-  const float* base = a.qkv + (long)b * S * ld + h * TG_HD;
-  const float* dob = a.datt + (long)b * S * d + h * TG_HD;
-  const float scale = 1.0f / sqrtf((float)TG_HD);
-  float4 k4[4], v4[4];
-  const long kr = (long)min(k0 + r, S - 1) * ld + 16 * g;
-  f32_load_q(k4, k0 + r < S, base + d + kr);
-  f32_load_q(v4, k0 + r < S, base + 2 * d + kr);
-  f32x4 dk[4], dv[4];
+  const float* base = a.qkv + (long)b * S * ld + h * HD;
+  const float* dob = a.datt + (long)b * S * d + h * HD;
+  const float scale = 1.0f / sqrtf((float)HD);
+  float4 k4[NQ], v4[NQ];
+  const long kr = (long)min(k0 + r, S - 1) * ld + LC * g;
+  tg_load_row<HD>(k4, k0 + r < S, base + d + kr);
+  tg_load_row<HD>(v4, k0 + r < S, base + 2 * d + kr);
+  f32x4 dk[NQ], dv[NQ];
 #pragma unroll
-  for (int jt = 0; jt < 4; ++jt) dk[jt] = dv[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int jt = 0; jt < NQ; ++jt) dk[jt] = dv[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
   const float* st = a.stat + ((long)b * a.H + h) * S * 2;
   const float* dl = a.delta + ((long)b * a.H + h) * S;
   for (int q0 = 0; q0 < S; q0 += 16) {
     const int q = q0 + r, qc = min(q, S - 1);
     const bool in = q < S;
-    const f32x4 sc = f32_score_tile(k4, base + (long)qc * ld + 16 * g, in);    // element e: key 4g + e against query r
-    const f32x4 dpv = f32_score_tile(v4, dob + (long)qc * d + 16 * g, in);
+    const f32x4 sc = tg_score_tile<HD>(k4, base + (long)qc * ld + LC * g, in);    // element e: key 4g + e against query r
+    const f32x4 dpv = tg_score_tile<HD>(v4, dob + (long)qc * d + LC * g, in);
     const float mx = st[2 * qc], inv = 1.0f / st[2 * qc + 1], del = dl[qc];
     __syncthreads();
 #pragma unroll
@@ -476,16 +516,16 @@ __global__ __launch_bounds__(64) void tg_attn_bwd_kv_kernel(const TgAttn a) {
       td[(4 * g + e) * TG_PLD + r] = ds;
     }
     __syncthreads();
-    tg_tile_mma(tp, dob, d, q0, S, r, g, dv);
-    tg_tile_mma(td, base, ld, q0, S, r, g, dk);
+    tg_tile_mma<HD>(tp, dob, d, q0, S, r, g, dv);
+    tg_tile_mma<HD>(td, base, ld, q0, S, r, g, dk);
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int k = k0 + 4 * g + e;
     if (k >= S) continue;
-    float* o = a.dqkv + ((long)b * S + k) * ld + h * TG_HD;
+    float* o = a.dqkv + ((long)b * S + k) * ld + h * HD;
 #pragma unroll
-    for (int jt = 0; jt < 4; ++jt) {
+    for (int jt = 0; jt < NQ; ++jt) {
       o[d + 16 * jt + r] = dk[jt][e];
       o[2 * d + 16 * jt + r] = dv[jt][e];
     }

@@ -11,9 +11,11 @@ that description:
   ENCTRAIN csrc/tamf_enctrain.hip -> libtamf_enctrain.so (include/tamf_enctrain.h: the SegmentEncoder training step - forward, loss, gradients)
   CONTACT  csrc/tamf_contact.hip -> libtamf_contact.so (include/tamf_contact.h: the contact-distance kernels of the training losses)
   REFINETRAIN csrc/tamf_refinetrain.hip -> libtamf_refinetrain.so (include/tamf_refinetrain.h: the SegmentRefineModel training step - forward, backward)
+  MDMTRAIN csrc/tamf_mdmtrain.hip -> libtamf_mdmtrain.so (include/tamf_mdmtrain.h: the InterationSegmentMDM training step - forward, backward)
 POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
 score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
-ENCTRAIN and REFINETRAIN share tamf_train_host.h (the table of bound tensors, the context base, the call checks, the launcher).
+ENCTRAIN, REFINETRAIN and MDMTRAIN share tamf_train_host.h (the table of bound tensors, the context base, the call checks, the
+launcher); REFINETRAIN and MDMTRAIN share tamf_trunk_host.h (the layer stack over the kernels of tamf_trunk_grad.h).
 Every library has its own sources, stamp and lock: building or loading one never touches another."""
 from __future__ import annotations
 
@@ -38,6 +40,7 @@ TEXTENC_LIB_PATH = os.path.join(LIB_DIR, "libtamf_textenc.so")
 ENCTRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_enctrain.so")
 CONTACT_LIB_PATH = os.path.join(LIB_DIR, "libtamf_contact.so")
 REFINETRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_refinetrain.so")
+MDMTRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_mdmtrain.so")
 
 EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_ctx_create", "tamf_ctx_resize", "tamf_ctx_destroy", "tamf_last_error", "tamf_load_weight", "tamf_finalize_weights",
@@ -76,6 +79,10 @@ CONTACT_EXPORTS = [  # include/tamf_contact.h: what libtamf_contact.so exports
 REFINETRAIN_EXPORTS = [  # include/tamf_refinetrain.h: what libtamf_refinetrain.so exports
     "tamf_refinetrain_last_error", "tamf_refinetrain_create", "tamf_refinetrain_destroy", "tamf_refinetrain_bind", "tamf_refinetrain_forward",
     "tamf_refinetrain_backward", "tamf_refinetrain_dropout_mask", "tamf_refinetrain_set_profile", "tamf_refinetrain_get_profile",
+]
+MDMTRAIN_EXPORTS = [  # include/tamf_mdmtrain.h: what libtamf_mdmtrain.so exports
+    "tamf_mdmtrain_last_error", "tamf_mdmtrain_create", "tamf_mdmtrain_destroy", "tamf_mdmtrain_bind", "tamf_mdmtrain_forward",
+    "tamf_mdmtrain_backward", "tamf_mdmtrain_dropout_mask", "tamf_mdmtrain_set_profile", "tamf_mdmtrain_get_profile",
 ]
 
 
@@ -284,16 +291,22 @@ REFINETRAIN = Library("libtamf_refinetrain", "tamf_refinetrain.hip", ("tamf_refi
                       (Output("libtamf_refinetrain.so", (), REFINETRAIN_EXPORTS),),
                       kernels=("_Z13tg_lin_kernelILb0EE", "_Z13tg_lin_kernelILb1EE", "_Z15tg_wgrad_kernel", "_Z18tg_attn_fwd_kernel", "_Z20tg_attn_bwd_q_kernel",
                                "_Z21tg_attn_bwd_kv_kernel"))
+MDMTRAIN = Library("libtamf_mdmtrain", "tamf_mdmtrain.hip", ("tamf_mdmtrain.h", "tamf_hip.h"),  # (tamf_hip.h for tamf_status and tamf_arch)
+                   (Output("libtamf_mdmtrain.so", (), MDMTRAIN_EXPORTS),),
+                   kernels=("_Z13tg_lin_kernelILb0EE", "_Z13tg_lin_kernelILb1EE", "_Z15tg_wgrad_kernel", "_Z18tg_attn_fwd_kernelILi64EE",
+                            "_Z18tg_attn_fwd_kernelILi128EE", "_Z20tg_attn_bwd_q_kernelILi64EE", "_Z20tg_attn_bwd_q_kernelILi128EE",
+                            "_Z21tg_attn_bwd_kv_kernelILi64EE", "_Z21tg_attn_bwd_kv_kernelILi128EE"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)
 TRAINING = (ENCTRAIN, CONTACT)  # the SegmentEncoder training step (launch/train_encoder.py); the contact-distance losses (contact.py)
 REFINE_TRAINING = (REFINETRAIN,)  # the refiner's training step (model/segment_refine_train.py); a group of its own: tests pin TRAINING to two
+DENOISER_TRAINING = (MDMTRAIN,)  # the denoiser's training step (model/interaction_segment_mdm_train.py); a group of its own for the same reason
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Every library, the sampler pair first, each only when ITS sources changed.  One library at a time.  Returns LIB_PATH."""
-    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING:
+    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING:
         lib.build(force, verbose)
     return LIB_PATH
 
@@ -365,6 +378,11 @@ def load_contact() -> ctypes.CDLL:
 def load_refinetrain() -> ctypes.CDLL:
     """libtamf_refinetrain.so (include/tamf_refinetrain.h).  Independent of the other libraries."""
     return _load(REFINETRAIN, "libtamf_refinetrain.so")
+
+
+def load_mdmtrain() -> ctypes.CDLL:
+    """libtamf_mdmtrain.so (include/tamf_mdmtrain.h).  Independent of the other libraries."""
+    return _load(MDMTRAIN, "libtamf_mdmtrain.so")
 
 
 def load_from(path: str) -> ctypes.CDLL:
