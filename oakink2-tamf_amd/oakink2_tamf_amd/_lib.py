@@ -12,6 +12,7 @@ that description:
   CONTACT  csrc/tamf_contact.hip -> libtamf_contact.so (include/tamf_contact.h: the contact-distance kernels of the training losses)
   REFINETRAIN csrc/tamf_refinetrain.hip -> libtamf_refinetrain.so (include/tamf_refinetrain.h: the SegmentRefineModel training step - forward, backward)
   MDMTRAIN csrc/tamf_mdmtrain.hip -> libtamf_mdmtrain.so (include/tamf_mdmtrain.h: the InterationSegmentMDM training step - forward, backward)
+  OPTIM    csrc/tamf_optim.hip -> libtamf_optim.so (include/tamf_optim.h: per-parameter gradient clipping + AdamW over a tensor table)
 POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
 score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
 ENCTRAIN, REFINETRAIN and MDMTRAIN share tamf_train_host.h (the table of bound tensors, the context base, the call checks, the
@@ -41,6 +42,7 @@ ENCTRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_enctrain.so")
 CONTACT_LIB_PATH = os.path.join(LIB_DIR, "libtamf_contact.so")
 REFINETRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_refinetrain.so")
 MDMTRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_mdmtrain.so")
+OPTIM_LIB_PATH = os.path.join(LIB_DIR, "libtamf_optim.so")
 
 EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_ctx_create", "tamf_ctx_resize", "tamf_ctx_destroy", "tamf_last_error", "tamf_load_weight", "tamf_finalize_weights",
@@ -83,6 +85,9 @@ REFINETRAIN_EXPORTS = [  # include/tamf_refinetrain.h: what libtamf_refinetrain.
 MDMTRAIN_EXPORTS = [  # include/tamf_mdmtrain.h: what libtamf_mdmtrain.so exports
     "tamf_mdmtrain_last_error", "tamf_mdmtrain_create", "tamf_mdmtrain_destroy", "tamf_mdmtrain_bind", "tamf_mdmtrain_forward",
     "tamf_mdmtrain_backward", "tamf_mdmtrain_dropout_mask", "tamf_mdmtrain_set_profile", "tamf_mdmtrain_get_profile",
+]
+OPTIM_EXPORTS = [  # include/tamf_optim.h: what libtamf_optim.so exports
+    "tamf_optim_last_error", "tamf_optim_create", "tamf_optim_destroy", "tamf_optim_bind", "tamf_optim_grad_norms", "tamf_optim_step",
 ]
 
 
@@ -296,17 +301,21 @@ MDMTRAIN = Library("libtamf_mdmtrain", "tamf_mdmtrain.hip", ("tamf_mdmtrain.h", 
                    kernels=("_Z13tg_lin_kernelILb0EE", "_Z13tg_lin_kernelILb1EE", "_Z15tg_wgrad_kernel", "_Z18tg_attn_fwd_kernelILi64EE",
                             "_Z18tg_attn_fwd_kernelILi128EE", "_Z20tg_attn_bwd_q_kernelILi64EE", "_Z20tg_attn_bwd_q_kernelILi128EE",
                             "_Z21tg_attn_bwd_kv_kernelILi64EE", "_Z21tg_attn_bwd_kv_kernelILi128EE"))
+OPTIM = Library("libtamf_optim", "tamf_optim.hip", ("tamf_optim.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
+                (Output("libtamf_optim.so", (), OPTIM_EXPORTS),),
+                kernels=("_Z18optim_sumsq_kernel", "_Z19optim_update_kernel", "_Z17optim_norm_kernel"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)
 TRAINING = (ENCTRAIN, CONTACT)  # the SegmentEncoder training step (launch/train_encoder.py); the contact-distance losses (contact.py)
 REFINE_TRAINING = (REFINETRAIN,)  # the refiner's training step (model/segment_refine_train.py); a group of its own: tests pin TRAINING to two
 DENOISER_TRAINING = (MDMTRAIN,)  # the denoiser's training step (model/interaction_segment_mdm_train.py); a group of its own for the same reason
+OPTIMISER = (OPTIM,)  # the optimiser step of the train / train_refine launchers (optim.py); a group of its own for the same reason
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Every library, the sampler pair first, each only when ITS sources changed.  One library at a time.  Returns LIB_PATH."""
-    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING:
+    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING + OPTIMISER:
         lib.build(force, verbose)
     return LIB_PATH
 
@@ -383,6 +392,11 @@ def load_refinetrain() -> ctypes.CDLL:
 def load_mdmtrain() -> ctypes.CDLL:
     """libtamf_mdmtrain.so (include/tamf_mdmtrain.h).  Independent of the other libraries."""
     return _load(MDMTRAIN, "libtamf_mdmtrain.so")
+
+
+def load_optim() -> ctypes.CDLL:
+    """libtamf_optim.so (include/tamf_optim.h).  Independent of the other libraries."""
+    return _load(OPTIM, "libtamf_optim.so")
 
 
 def load_from(path: str) -> ctypes.CDLL:
