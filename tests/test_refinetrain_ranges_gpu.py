@@ -1,0 +1,46 @@
+"""The refiner's training step (libtamf_refinetrain.so) on the MI355X over the accepted architecture ranges and their edges: the cases of
+tests/trunk_train_cases.py (head counts 3, 5, 8, the ff_size tails, widths 1, odd and 4096, 64 layers, S = 1023 and 1024, the token-row
+counts at which the weight-gradient split changes and where splits are empty, 300 one-frame clips, 1 and 5 objects) against float64
+autograd through the oracle, every gradient element written; dropout with the library's own masks at 8 heads, ff_size 80 and S = 1023;
+a clip's forward bits alone and inside a batch, and a repeated call's gradient bits where splits are empty.  The helpers are
+tests/test_refinetrain_gpu.py's; the bodies are shared with tests/test_mdmtrain_ranges_gpu.py.
+
+Gates: trunk_train_cases.gates - 4 x the oracle's float32 autograd against its float64 autograd, measured at test time and printed,
+capped at the largest fixture gate except for the gradients of trunk_train_cases.UNCAPPED_GRAD (R-w1, R-l64) and the output of
+trunk_train_cases.UNCAPPED_OUT (R-h3, R-h5, R-l64), where the float32 oracle itself lies outside the cap.  The errors measured on the
+MI355X are in the table of DESIGN.md section 4."""
+import os
+import sys
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import test_refinetrain_gpu as TM  # noqa: E402
+import trunk_train_cases as C  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+LIB = "R"
+
+
+@pytest.mark.parametrize("case", C.CASES[LIB], ids=lambda c: c.id)
+def test_parity_with_oracle_autograd(case):
+    C.check_parity(TM, case)
+
+
+@pytest.mark.parametrize("name", C.DROPOUT_CASES)
+def test_dropout_with_the_librarys_masks(name):
+    C.check_dropout(TM, C.BY_ID[f"{LIB}-{name}"])
+
+
+def test_attention_masks_differ_between_head_0_and_head_4():
+    C.check_head_masks_differ(TM, C.BY_ID[f"{LIB}-h8"])
+
+
+@pytest.mark.parametrize("name", C.BATCH_BIT_CASES)
+def test_a_clip_alone_has_the_bits_of_the_clip_in_a_batch(name):
+    C.check_batch_bits(TM, C.BY_ID[f"{LIB}-{name}"])
+
+
+def test_empty_splits_give_the_same_bits_twice():
+    C.check_repeat_bits(TM, C.BY_ID[f"{LIB}-{C.REPEAT_BIT_CASE}"])
