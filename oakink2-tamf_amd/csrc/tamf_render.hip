@@ -1,0 +1,154 @@
+// libtamf_render.so: the C-ABI of include/tamf_render.h - the offscreen renderer.  One translation unit.
+#include "../../include/tamf_render.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+
+#include "tamf_raster.h"
+
+static_assert(TAMF_RENDER_MAX_LIGHTS == RS_MAX_LIGHTS, "the header's light count is the kernels'");
+
+static thread_local std::string g_render_error;
+
+static int fail(int code, const std::string& msg) {
+  g_render_error = msg;
+  return code;
+}
+
+extern "C" const char* tamf_render_last_error(void) { return g_render_error.c_str(); }
+
+constexpr long RN_INT_MAX = 2147483647L;
+
+// the limits of include/tamf_render.h on a (F, H, W) buffer; "" when accepted
+static std::string bad_image(int F, int H, int W) {
+  const std::string dims = "F = " + std::to_string(F) + ", H = " + std::to_string(H) + ", W = " + std::to_string(W);
+  if (W < 1 || W > TAMF_RENDER_MAX_SIDE || H < 1 || H > TAMF_RENDER_MAX_SIDE)
+    return "W and H must lie in [1, " + std::to_string(TAMF_RENDER_MAX_SIDE) + "] (" + dims + ")";
+  if (F < 1 || F > 65535) return "F outside [1, 65535] (" + dims + ")";
+  if ((long)F * H * W > RN_INT_MAX) return "F * H * W above 2^31 - 1: split the frames (" + dims + ")";
+  return "";
+}
+
+// on F frames of n elements (vertices or points) and `count` primitives numbered from prim_base
+static std::string bad_prims(int F, int n, int count, int prim_base) {
+  const std::string dims = "F = " + std::to_string(F) + ", elements = " + std::to_string(n) + ", primitives = " + std::to_string(count) +
+                           ", prim_base = " + std::to_string(prim_base);
+  if (n < 1 || count < 1) return "a mesh needs at least one vertex and one face, a cloud one point (" + dims + ")";
+  if ((long)F * n > RN_INT_MAX / 3 || count > RN_INT_MAX / 3) return "F * V (or F * P), or the face count, above (2^31 - 1) / 3 (" + dims + ")";
+  if (prim_base < 0 || (long)prim_base + count > RN_INT_MAX) return "prim_base < 0 or prim_base + count above 2^31 - 1 (" + dims + ")";
+  return "";
+}
+
+static int launched() {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(TAMF_ERR_HIP, hipGetErrorString(e));
+  return 0;
+}
+
+static dim3 tiles(int F, int H, int W) { return dim3((W + RS_TILE - 1) / RS_TILE, (H + RS_TILE - 1) / RS_TILE, F); }
+static unsigned blocks(long n) { return (unsigned)((n + 255) / 256); }
+static int to_byte(float c) { return (int)std::floor(255.0f * std::fmin(std::fmax(c, 0.0f), 1.0f) + 0.5f); }
+static bool finite3(const float* c) { return std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]); }
+
+extern "C" int tamf_render_project(const float* verts, const float* model, const tamf_render_camera* camera, int32_t F, int32_t V,
+                                   int32_t per_frame, float* pos_cam, int32_t* xy, void* stream) {
+  if (!verts || !camera || !pos_cam || !xy) return fail(TAMF_ERR_INVALID, "null argument: verts, camera, pos_cam_out and xy_out are required");
+  if (F < 1 || F > 65535 || V < 1 || (long)F * V > RN_INT_MAX / 3)
+    return fail(TAMF_ERR_INVALID, "F outside [1, 65535], V < 1 or F * V above (2^31 - 1) / 3 (F = " + std::to_string(F) + ", V = " + std::to_string(V) + ")");
+  RsCamera cam;
+  for (int i = 0; i < 12; ++i) {
+    if (!std::isfinite(camera->view[i])) return fail(TAMF_ERR_INVALID, "camera: a non-finite view entry");
+    cam.view[i] = camera->view[i];
+  }
+  cam.fx = camera->fx, cam.fy = camera->fy, cam.cx = camera->cx, cam.cy = camera->cy, cam.near = camera->near;
+  if (!std::isfinite(cam.fx) || !std::isfinite(cam.fy) || !std::isfinite(cam.cx) || !std::isfinite(cam.cy))
+    return fail(TAMF_ERR_INVALID, "camera: non-finite intrinsics");
+  if (!(cam.near > 0.0f) || !std::isfinite(cam.near)) return fail(TAMF_ERR_INVALID, "camera: near must be positive and finite");
+  hipLaunchKernelGGL(render_project_kernel, dim3(blocks((long)F * V)), dim3(256), 0, (hipStream_t)stream, verts, model, cam, F, V,
+                     per_frame ? 1 : 0, pos_cam, (int*)xy);
+  return launched();
+}
+
+extern "C" int tamf_render_clear(float* depth, int32_t* prim_id, int32_t F, int32_t H, int32_t W, void* stream) {
+  if (!depth || !prim_id) return fail(TAMF_ERR_INVALID, "null argument: depth and prim_id are required");
+  const std::string bad = bad_image(F, H, W);
+  if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
+  const long n = (long)F * H * W;
+  hipLaunchKernelGGL(render_clear_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, depth, (int*)prim_id, n);
+  return launched();
+}
+
+extern "C" int tamf_render_raster(const int32_t* xy, const float* pos_cam, const int32_t* faces, int32_t F, int32_t V, int32_t Nf, int32_t H,
+                                  int32_t W, int32_t prim_base, float* depth, int32_t* prim_id, void* stream) {
+  if (!xy || !pos_cam || !faces || !depth || !prim_id) return fail(TAMF_ERR_INVALID, "null argument: xy, pos_cam, faces, depth and prim_id are required");
+  std::string bad = bad_image(F, H, W);
+  if (bad.empty()) bad = bad_prims(F, V, Nf, prim_base);
+  if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
+  hipLaunchKernelGGL(render_raster_kernel, tiles(F, H, W), dim3(RS_NT), 0, (hipStream_t)stream, (const int*)xy, pos_cam, (const int*)faces, Nf, V,
+                     W, H, prim_base, depth, (int*)prim_id);
+  return launched();
+}
+
+extern "C" int tamf_render_points(const int32_t* xy, const float* pos_cam, int32_t F, int32_t P, int32_t H, int32_t W, int32_t point_size,
+                                  int32_t prim_base, float* depth, int32_t* prim_id, void* stream) {
+  if (!xy || !pos_cam || !depth || !prim_id) return fail(TAMF_ERR_INVALID, "null argument: xy, pos_cam, depth and prim_id are required");
+  std::string bad = bad_image(F, H, W);
+  if (bad.empty()) bad = bad_prims(F, P, P, prim_base);
+  if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
+  if (point_size < 1 || point_size > TAMF_RENDER_MAX_POINT_SIZE || point_size % 2 == 0)
+    return fail(TAMF_ERR_INVALID, "point_size must be odd and lie in [1, " + std::to_string(TAMF_RENDER_MAX_POINT_SIZE) + "], got " + std::to_string(point_size));
+  hipLaunchKernelGGL(render_points_kernel, tiles(F, H, W), dim3(RS_NT), 0, (hipStream_t)stream, (const int*)xy, pos_cam, P, W, H, point_size / 2,
+                     prim_base, depth, (int*)prim_id);
+  return launched();
+}
+
+extern "C" int tamf_render_shade_mesh(const int32_t* prim_id, const int32_t* xy, const float* pos_cam, const float* normals, const int32_t* faces,
+                                      int32_t F, int32_t V, int32_t Nf, int32_t H, int32_t W, int32_t prim_base, const float* base_rgb, float ambient,
+                                      const float* lights, int32_t L, uint8_t* rgb, void* stream) {
+  if (!prim_id || !xy || !pos_cam || !faces || !base_rgb || !rgb)
+    return fail(TAMF_ERR_INVALID, "null argument: prim_id, xy, pos_cam, faces, base_rgb and rgb are required");
+  if (L < 0 || L > RS_MAX_LIGHTS || (L > 0 && !lights))
+    return fail(TAMF_ERR_INVALID, "L outside [0, " + std::to_string(RS_MAX_LIGHTS) + "], or lights null with L > 0 (L = " + std::to_string(L) + ")");
+  std::string bad = bad_image(F, H, W);
+  if (bad.empty()) bad = bad_prims(F, V, Nf, prim_base);
+  if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
+  if (!finite3(base_rgb) || !std::isfinite(ambient)) return fail(TAMF_ERR_INVALID, "non-finite base colour or ambient term");
+  RsLights Ls = {};
+  Ls.ambient = ambient;
+  Ls.n = L;
+  for (int l = 0; l < L; ++l) {
+    if (!finite3(lights + 4 * l) || !std::isfinite(lights[4 * l + 3])) return fail(TAMF_ERR_INVALID, "light " + std::to_string(l) + " is not finite");
+    for (int c = 0; c < 3; ++c) Ls.dir[l][c] = lights[4 * l + c];
+    Ls.strength[l] = lights[4 * l + 3];
+  }
+  const long n = (long)F * H * W;
+  hipLaunchKernelGGL(render_shade_mesh_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, (const int*)prim_id, (const int*)xy, pos_cam, normals,
+                     (const int*)faces, Nf, V, F, W, H, prim_base, base_rgb[0], base_rgb[1], base_rgb[2], Ls, rgb);
+  return launched();
+}
+
+extern "C" int tamf_render_shade_points(const int32_t* prim_id, int32_t F, int32_t H, int32_t W, int32_t prim_base, int32_t P, const float* base_rgb,
+                                        uint8_t* rgb, void* stream) {
+  if (!prim_id || !base_rgb || !rgb) return fail(TAMF_ERR_INVALID, "null argument: prim_id, base_rgb and rgb are required");
+  std::string bad = bad_image(F, H, W);
+  if (bad.empty()) bad = bad_prims(F, 1, P, prim_base);
+  if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
+  if (!finite3(base_rgb)) return fail(TAMF_ERR_INVALID, "non-finite base colour");
+  const long n = (long)F * H * W;
+  hipLaunchKernelGGL(render_shade_points_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, (const int*)prim_id, n, prim_base, P,
+                     to_byte(base_rgb[0]), to_byte(base_rgb[1]), to_byte(base_rgb[2]), rgb);
+  return launched();
+}
+
+extern "C" int tamf_render_fill(const int32_t* prim_id, int32_t F, int32_t H, int32_t W, const float* bg_rgb, uint8_t* rgb, void* stream) {
+  if (!prim_id || !bg_rgb || !rgb) return fail(TAMF_ERR_INVALID, "null argument: prim_id, bg_rgb and rgb are required");
+  const std::string bad = bad_image(F, H, W);
+  if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
+  if (!finite3(bg_rgb)) return fail(TAMF_ERR_INVALID, "non-finite background colour");
+  const long n = (long)F * H * W;
+  hipLaunchKernelGGL(render_fill_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, (const int*)prim_id, rgb, n, to_byte(bg_rgb[0]),
+                     to_byte(bg_rgb[1]), to_byte(bg_rgb[2]));
+  return launched();
+}

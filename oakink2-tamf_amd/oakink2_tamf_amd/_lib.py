@@ -13,6 +13,7 @@ that description:
   REFINETRAIN csrc/tamf_refinetrain.hip -> libtamf_refinetrain.so (include/tamf_refinetrain.h: the SegmentRefineModel training step - forward, backward)
   MDMTRAIN csrc/tamf_mdmtrain.hip -> libtamf_mdmtrain.so (include/tamf_mdmtrain.h: the InterationSegmentMDM training step - forward, backward)
   OPTIM    csrc/tamf_optim.hip -> libtamf_optim.so (include/tamf_optim.h: per-parameter gradient clipping + AdamW over a tensor table)
+  RENDER   csrc/tamf_render.hip -> libtamf_render.so (include/tamf_render.h: projection, triangle / point rasteriser, Lambert shading)
 POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
 score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
 ENCTRAIN, REFINETRAIN and MDMTRAIN share tamf_train_host.h (the table of bound tensors, the context base, the call checks, the
@@ -43,6 +44,7 @@ CONTACT_LIB_PATH = os.path.join(LIB_DIR, "libtamf_contact.so")
 REFINETRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_refinetrain.so")
 MDMTRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_mdmtrain.so")
 OPTIM_LIB_PATH = os.path.join(LIB_DIR, "libtamf_optim.so")
+RENDER_LIB_PATH = os.path.join(LIB_DIR, "libtamf_render.so")
 
 EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_ctx_create", "tamf_ctx_resize", "tamf_ctx_destroy", "tamf_last_error", "tamf_load_weight", "tamf_finalize_weights",
@@ -88,6 +90,10 @@ MDMTRAIN_EXPORTS = [  # include/tamf_mdmtrain.h: what libtamf_mdmtrain.so export
 ]
 OPTIM_EXPORTS = [  # include/tamf_optim.h: what libtamf_optim.so exports
     "tamf_optim_last_error", "tamf_optim_create", "tamf_optim_destroy", "tamf_optim_bind", "tamf_optim_grad_norms", "tamf_optim_step",
+]
+RENDER_EXPORTS = [  # include/tamf_render.h: what libtamf_render.so exports
+    "tamf_render_last_error", "tamf_render_project", "tamf_render_clear", "tamf_render_raster", "tamf_render_points", "tamf_render_shade_mesh",
+    "tamf_render_shade_points", "tamf_render_fill",
 ]
 
 
@@ -304,6 +310,9 @@ MDMTRAIN = Library("libtamf_mdmtrain", "tamf_mdmtrain.hip", ("tamf_mdmtrain.h", 
 OPTIM = Library("libtamf_optim", "tamf_optim.hip", ("tamf_optim.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
                 (Output("libtamf_optim.so", (), OPTIM_EXPORTS),),
                 kernels=("_Z18optim_sumsq_kernel", "_Z19optim_update_kernel", "_Z17optim_norm_kernel"))
+RENDER = Library("libtamf_render", "tamf_render.hip", ("tamf_render.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
+                 (Output("libtamf_render.so", (), RENDER_EXPORTS),),
+                 kernels=("_Z21render_project_kernel", "_Z20render_raster_kernel", "_Z20render_points_kernel", "_Z24render_shade_mesh_kernel"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)
@@ -311,11 +320,12 @@ TRAINING = (ENCTRAIN, CONTACT)  # the SegmentEncoder training step (launch/train
 REFINE_TRAINING = (REFINETRAIN,)  # the refiner's training step (model/segment_refine_train.py); a group of its own: tests pin TRAINING to two
 DENOISER_TRAINING = (MDMTRAIN,)  # the denoiser's training step (model/interaction_segment_mdm_train.py); a group of its own for the same reason
 OPTIMISER = (OPTIM,)  # the optimiser step of the train / train_refine launchers (optim.py); a group of its own for the same reason
+RENDERING = (RENDER,)  # the offscreen renderer behind launch/render_samples.py (render.py); a group of its own for the same reason
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Every library, the sampler pair first, each only when ITS sources changed.  One library at a time.  Returns LIB_PATH."""
-    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING + OPTIMISER:
+    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING + OPTIMISER + RENDERING:
         lib.build(force, verbose)
     return LIB_PATH
 
@@ -397,6 +407,11 @@ def load_mdmtrain() -> ctypes.CDLL:
 def load_optim() -> ctypes.CDLL:
     """libtamf_optim.so (include/tamf_optim.h).  Independent of the other libraries."""
     return _load(OPTIM, "libtamf_optim.so")
+
+
+def load_render() -> ctypes.CDLL:
+    """libtamf_render.so (include/tamf_render.h).  Independent of the other libraries."""
+    return _load(RENDER, "libtamf_render.so")
 
 
 def load_from(path: str) -> ctypes.CDLL:

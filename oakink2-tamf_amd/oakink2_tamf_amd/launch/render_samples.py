@@ -1,0 +1,164 @@
+"""Pictures of refined motions on MI355X: every clip with a refined sample rendered frame by frame, hand and objects, to PNG files.
+Stands where the reference's viewers (script/viz_seg.py, script/debug/debug_refine_sample.py, script/debug/debug_train_sample.py) open
+an Open3D window and dev_fn/util/vis_pyrender_util.py renders through OpenGL; a headless node has neither.
+
+    python -m oakink2_tamf_amd.launch.render_samples --data.process_range "?(file:./asset/split/test.txt)" \
+        --data.cache_dict_filepath common/save_cache_dict/main/cache/test.pkl \
+        --debug.sample_refine_filepath common/sample_refine/main/sample/test/arch_mdm_l__0399 --out_dir render/test/arch_mdm_l__0399 \
+        [--data.obj_model_loader pkg.mod:load_obj] [--with_gt --mano.factory pkg.mod:make_mano] [--render.width 512] [--render.height 512]
+        [--render.every 1] [--render.sheet_cols 8] [--render.point_size 3] [--max_clips N] [--device cuda:0] [--out_json index.json] [--dry_run]
+
+The `--data.*`, `--debug.sample_refine_filepath` and `--mano.*` names of compute_score_cr.py (launch/_score_common.py), and:
+  --data.obj_model_loader module:function   function(obj_id) -> (verts, faces), as compute_score_siv.py takes it: the objects are drawn
+                                            as meshes; without it as the splats of their `obj_pointcloud`
+  --with_gt                                 a second panel beside the refined one: the ground-truth hand (pose decode -> MANO) in a second
+                                            colour with the same objects and camera; needs --mano.factory and is refused without it
+Per clip: the refined hand is the save dict's `verts` over its `faces` (the --mano.factory tuple's closed faces when the save dict
+holds none), every object of `obj_list` moves along the item's `obj_traj`, frames 0, every, 2 every, ... of the first `len` frames are
+drawn from ONE camera fitted to everything in them (render.look_at_camera).  Output under
+<out_dir>/<process_key with '/' -> '++'>/<info[1]>/<info[2]>/: frame_%04d.png per drawn frame (numbered by clip frame) and sheet.png,
+every sheet_cols-th drawn frame tiled sheet_cols to a row.  The image is this package's rasterisation and Lambert shading, not
+pyrender's (render.py)."""
+from __future__ import annotations
+
+import json
+import logging
+import os
+import sys
+
+import numpy as np
+
+from . import _score_common as C
+from . import formats
+from .compute_score_siv import resolve_loader
+
+_logger = logging.getLogger("oakink2_tamf_amd.launch.render_samples")
+PROG = "render_samples"
+HAND_COLOR, GT_HAND_COLOR = (0.91, 0.72, 0.60), (0.45, 0.65, 0.90)
+OBJ_COLORS = ((0.55, 0.80, 0.45), (0.90, 0.55, 0.35), (0.70, 0.55, 0.85), (0.85, 0.80, 0.40))
+RENDER_DEFAULTS = {"width": 512, "height": 512, "every": 1, "sheet_cols": 8, "point_size": 3}
+
+
+def parse_args(argv):
+    ap = C.make_parser(PROG)
+    ap.add_argument("--data.obj_model_loader", dest="data__obj_model_loader", default=None,
+                    help="module:function, function(obj_id) -> (verts, faces): draw the objects as meshes")
+    for key, default in RENDER_DEFAULTS.items():
+        ap.add_argument("--render." + key, dest="render__" + key, type=int, default=default)
+    ap.add_argument("--out_dir", default=os.path.join("common", "render_samples", "main"))
+    ap.add_argument("--max_clips", type=int, default=None, help="render the first N clips only")
+    ap.add_argument("--with_gt", action="store_true", help="second panel: the ground-truth hand (needs --mano.factory)")
+    a = ap.parse_args(argv)
+    cfg = C.build_config(a)
+    cfg["data"]["obj_model_loader"] = a.data__obj_model_loader
+    r = {key: getattr(a, "render__" + key) for key in RENDER_DEFAULTS}
+    if not (1 <= r["width"] <= 4096 and 1 <= r["height"] <= 4096):
+        ap.error("--render.width and --render.height must lie in [1, 4096]")
+    if r["every"] < 1 or r["sheet_cols"] < 1:
+        ap.error("--render.every and --render.sheet_cols must be at least 1")
+    if r["point_size"] % 2 != 1 or not 1 <= r["point_size"] <= 15:
+        ap.error("--render.point_size must be odd and lie in [1, 15]")
+    if a.max_clips is not None and a.max_clips < 1:
+        ap.error("--max_clips must be at least 1")
+    if a.with_gt and not cfg["mano"]["factory"]:
+        ap.error("--with_gt draws the ground-truth hand through MANO: pass --mano.factory module:function")
+    cfg["render"] = r
+    cfg["runtime"].update(out_dir=os.path.abspath(a.out_dir), max_clips=a.max_clips, with_gt=a.with_gt)
+    return cfg
+
+
+def clip_dir(out_dir: str, info) -> str:
+    return os.path.join(out_dir, str(info[0]).replace("/", "++"), str(info[1]), str(info[2]))
+
+
+def drawn_frames(length: int, every: int):
+    return list(range(0, int(length), every))
+
+
+def render_clip(item, hands, faces, cfg, device):
+    """hands: [(verts (T, 778, 3), colour)], one panel each -> (frames, images (n, H, panels * W, 3) uint8 numpy)"""
+    from .. import render as R
+
+    r = cfg["render"]
+    frames = drawn_frames(item["len"], r["every"])
+    if not frames:
+        return frames, None
+    poses = [R.tslrot6d_to_matrix(np.asarray(item["obj_traj"])[k]) for k in range(len(item["obj_list"]))]
+    meshes = "obj_verts" in item
+    shapes = [np.asarray(item["obj_verts"][k] if meshes else item["obj_pointcloud"][k], np.float64) for k in range(len(item["obj_list"]))]
+    seen = [np.asarray(h, np.float64)[frames].reshape(-1, 3) for h, _ in hands]
+    for m, s in zip(poses, shapes):
+        seen.append((np.einsum("fij,pj->fpi", m[frames][:, :, :3], s) + m[frames][:, None, :, 3]).reshape(-1, 3))
+    cam = R.look_at_camera(np.concatenate(seen), r["width"], r["height"])
+    panels = []
+    for verts, colour in hands:
+        rd = R.HipRenderer(r["width"], r["height"], device)
+        rd.add_mesh(np.asarray(verts, np.float32)[frames], faces, color=colour, smooth=True, name="hand")
+        for k, (m, s) in enumerate(zip(poses, shapes)):
+            colour_k = OBJ_COLORS[k % len(OBJ_COLORS)]
+            if meshes:
+                rd.add_mesh(s, item["obj_faces"][k], color=colour_k, pose=m[frames], name=str(item["obj_list"][k]))
+            else:
+                rd.add_points(s, color=colour_k, pose=m[frames], point_size=r["point_size"], name=str(item["obj_list"][k]))
+        panels.append(rd.render(cam)[0].cpu().numpy())
+    return frames, np.concatenate(panels, axis=2)
+
+
+def main(argv=None) -> int:
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    cfg = parse_args(sys.argv[1:] if argv is None else argv)
+    rt = cfg["runtime"]
+    loader = resolve_loader(cfg["data"]["obj_model_loader"])
+    pairs = C.load_pairs(cfg, obj_model_loader=loader)
+    if rt["max_clips"] is not None:
+        pairs = pairs[: rt["max_clips"]]
+    _logger.info("clips with a refined sample: %d", len(pairs))
+    if rt["dry_run"]:
+        print(json.dumps({"n_clips": len(pairs), "pairs": C.pair_listing(pairs), "sample_refine_filepath": cfg["debug"]["sample_refine_filepath"],
+                          "obj_model_loader": cfg["data"]["obj_model_loader"], "out_dir": rt["out_dir"], "render": cfg["render"],
+                          "with_gt": rt["with_gt"]}))
+        return 0
+    import torch
+
+    from .. import render as R
+
+    device = torch.device(rt["device"])
+    mano = C.load_mano(cfg, device) if cfg["mano"]["factory"] else None
+    if not pairs:
+        raise SystemExit(f"no clip with a refined sample under {cfg['debug']['sample_refine_filepath']}")
+    torch.cuda.set_device(device)
+    items = [p[0] for p in pairs]
+    gt_verts = C.ground_truth_mano(items, mano, device, rt["batch_size"])[1] if rt["with_gt"] else [None] * len(items)
+    index = []
+    for (item, path), gt in zip(pairs, gt_verts):
+        save = formats.read_refine_sample(path)
+        faces = save.get("faces")
+        if faces is None:
+            if mano is None:
+                raise SystemExit(f"{path} holds no hand faces: pass --mano.factory module:function (its closed faces are used)")
+            faces = mano[2] if item["hand_side"] == "rh" else mano[3]
+        hands = [(np.asarray(save["verts"], np.float32), HAND_COLOR)] + ([(gt, GT_HAND_COLOR)] if gt is not None else [])
+        frames, images = render_clip(item, hands, np.asarray(faces), cfg, device)
+        out = clip_dir(rt["out_dir"], item["info"])
+        entry = {"info": list(item["info"]), "dir": out, "frames": frames, "files": [], "sheet": None,
+                 "objects": "mesh" if "obj_verts" in item else "points"}
+        if frames:
+            os.makedirs(out, exist_ok=True)
+            for k, fr in enumerate(frames):
+                name = "frame_%04d.png" % fr
+                R.write_png(os.path.join(out, name), images[k])
+                entry["files"].append(name)
+            R.write_png(os.path.join(out, "sheet.png"), R.contact_sheet(images[:: cfg["render"]["sheet_cols"]], cfg["render"]["sheet_cols"]))
+            entry["sheet"] = "sheet.png"
+        index.append(entry)
+        print(f"{out} {len(frames)} frames")
+    res = {"n_clips": len(index), "n_frames": sum(len(e["frames"]) for e in index), "out_dir": rt["out_dir"], "render": cfg["render"],
+           "with_gt": rt["with_gt"], "clips": index}
+    print(f"n_frames {res['n_frames']}")
+    if rt["out_json"]:
+        C.write_json(rt["out_json"], res)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
