@@ -11,6 +11,12 @@
 // Coverage is exact: the edge functions are int64 in 1/256-pixel units, evaluated once per triangle at the tile's first pixel
 // centre and stepped across the tile by whole pixels (A * 256 dx + B * 256 dy, one v_mad_i64_i32 each).  |coordinate| <= 2^28
 // (tamf_render_project's validity bound) keeps differences inside int32 and the edge functions inside int64 (< 2^59).
+//
+// Depth peeling: the rasteriser and the splatter take a template parameter FLOOR.  The FLOOR instantiation reads a floor (depth, id)
+// per pixel and admits only candidates that come strictly after it in the order (depth, id); everything else, the depth expression
+// included, is the one body, so a fragment's depth has the same bits in every pass.  The plain instantiation compiles to the code it
+// was before the parameter existed.  The colour passes are template parameters of the shading kernels in the same way.  Composite and
+// resolve are one thread per output pixel; the number of layers, items and sub-samples are host values: no loop runs on device data.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -156,19 +162,28 @@ struct RsTriSlot {
   int index;       // triangle index
 };
 
+// FLOOR: admit a candidate only where floor_id >= 0 and (d, id) comes strictly after (floor_depth, floor_id); both null otherwise
+template <bool FLOOR>
 __global__ void __launch_bounds__(RS_NT) render_raster_kernel(const int* __restrict__ xy, const float* __restrict__ pos_cam,
                                                              const int* __restrict__ faces, int Nf, int V, int W, int H, int prim_base,
-                                                             float* __restrict__ depth, int* __restrict__ prim_id) {
+                                                             float* __restrict__ depth, int* __restrict__ prim_id,
+                                                             const float* __restrict__ floor_depth, const int* __restrict__ floor_id) {
   __shared__ RsTriSlot slot[RS_NT];
   __shared__ int wave_count[RS_NT / 64];
   const int f = blockIdx.z;
   const int tx0 = blockIdx.x * RS_TILE, ty0 = blockIdx.y * RS_TILE;
   const int dx = threadIdx.x % RS_TILE, dy = threadIdx.x / RS_TILE;
   const int px = tx0 + dx, py = ty0 + dy;
-  const bool live = px < W && py < H;
+  bool live = px < W && py < H;
   const long pix = ((long)f * H + py) * W + px;
   const int* xy_f = xy + (long)f * V * 2;
   const float* pos_f = pos_cam + (long)f * V * 3;
+  float fd = 0.0f;
+  int fid = -1;
+  if constexpr (FLOOR) {
+    if (live) fd = floor_depth[pix], fid = floor_id[pix];
+    live = live && fid >= 0;  // nothing lies behind a pixel whose previous layer is empty
+  }
   // the tile's pixel centres in fixed point (clipped to the image: the overhang holds no pixel)
   const int cx0 = tx0 * RS_SUB + RS_SUB / 2, cy0 = ty0 * RS_SUB + RS_SUB / 2;
   const int cx1 = (min(tx0 + RS_TILE, W) - 1) * RS_SUB + RS_SUB / 2, cy1 = (min(ty0 + RS_TILE, H) - 1) * RS_SUB + RS_SUB / 2;
@@ -218,6 +233,9 @@ __global__ void __launch_bounds__(RS_NT) render_raster_kernel(const int* __restr
         if (e2 < 0 || (e2 == 0 && !(s.own & 4))) continue;
         const float inv_z = (float)e0 * s.q[0] + (float)e1 * s.q[1] + (float)e2 * s.q[2];
         const float d = 1.0f / inv_z;
+        if constexpr (FLOOR) {
+          if (!(d > fd || (d == fd && prim_base + s.index > fid))) continue;
+        }
         if (d < best) best = d, best_id = prim_base + s.index;
       }
     }
@@ -233,17 +251,25 @@ struct RsPointSlot {
   int index;
 };
 
+template <bool FLOOR>
 __global__ void __launch_bounds__(RS_NT) render_points_kernel(const int* __restrict__ xy, const float* __restrict__ pos_cam, int P, int W, int H,
-                                                             int half, int prim_base, float* __restrict__ depth, int* __restrict__ prim_id) {
+                                                             int half, int prim_base, float* __restrict__ depth, int* __restrict__ prim_id,
+                                                             const float* __restrict__ floor_depth, const int* __restrict__ floor_id) {
   __shared__ RsPointSlot slot[RS_NT];
   __shared__ int wave_count[RS_NT / 64];
   const int f = blockIdx.z;
   const int tx0 = blockIdx.x * RS_TILE, ty0 = blockIdx.y * RS_TILE;
   const int px = tx0 + threadIdx.x % RS_TILE, py = ty0 + threadIdx.x / RS_TILE;
-  const bool live = px < W && py < H;
+  bool live = px < W && py < H;
   const long pix = ((long)f * H + py) * W + px;
   const int* xy_f = xy + (long)f * P * 2;
   const float* pos_f = pos_cam + (long)f * P * 3;
+  float fd = 0.0f;
+  int fid = -1;
+  if constexpr (FLOOR) {
+    if (live) fd = floor_depth[pix], fid = floor_id[pix];
+    live = live && fid >= 0;
+  }
   const int tx1 = min(tx0 + RS_TILE, W) - 1, ty1 = min(ty0 + RS_TILE, H) - 1;
   float best = __builtin_inff();
   int best_id = -1;
@@ -274,6 +300,9 @@ __global__ void __launch_bounds__(RS_NT) render_points_kernel(const int* __restr
       for (int i = 0; i < n; ++i) {
         const RsPointSlot& s = slot[i];
         if (abs(px - s.px) > half || abs(py - s.py) > half) continue;
+        if constexpr (FLOOR) {
+          if (!(s.z > fd || (s.z == fd && prim_base + s.index > fid))) continue;
+        }
         if (s.z < best) best = s.z, best_id = prim_base + s.index;
       }
     }
@@ -288,11 +317,14 @@ __device__ inline unsigned char rs_byte(float base, float I) {
   return (unsigned char)floorf(255.0f * c + 0.5f);
 }
 
-// one thread per pixel of (F, H, W); writes only where prim_id lies in [prim_base, prim_base + Nf)
+// one thread per pixel of (F, H, W); writes only where prim_id lies in [prim_base, prim_base + Nf).  COLORS: the base colour is the
+// blend of vertex_rgb (V,3), or (F,V,3) when col_per_frame, by the weights of the normals, taken as c_0 + w_1 (c_1 - c_0) + w_2 (c_2 - c_0):
+// three equal colours give exactly that colour, and so the bytes of the constant-colour pass.
+template <bool COLORS>
 __global__ void __launch_bounds__(256) render_shade_mesh_kernel(const int* __restrict__ prim_id, const int* __restrict__ xy, const float* __restrict__ pos_cam,
                                                                 const float* __restrict__ normals, const int* __restrict__ faces, int Nf, int V, int F,
                                                                 int W, int H, int prim_base, float br, float bg, float bb, RsLights L,
-                                                                unsigned char* __restrict__ rgb) {
+                                                                unsigned char* __restrict__ rgb, const float* __restrict__ vertex_rgb, int col_per_frame) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)F * H * W) return;
   const int id = prim_id[i];
@@ -330,18 +362,83 @@ __global__ void __launch_bounds__(256) render_shade_mesh_kernel(const int* __res
     for (int c = 0; c < 3; ++c) n[c] *= s;
     for (int l = 0; l < L.n; ++l) I += L.strength[l] * fmaxf(0.0f, -(n[0] * L.dir[l][0] + n[1] * L.dir[l][1] + n[2] * L.dir[l][2]));
   }
+  if constexpr (COLORS) {
+    const float* cf = vertex_rgb + (col_per_frame ? (long)f * V * 3 : 0L);
+    const float* c0 = cf + (long)tri.v[0] * 3;
+    const float* c1 = cf + (long)tri.v[1] * 3;
+    const float* c2 = cf + (long)tri.v[2] * 3;
+    br = c0[0] + w[1] * (c1[0] - c0[0]) + w[2] * (c2[0] - c0[0]);
+    bg = c0[1] + w[1] * (c1[1] - c0[1]) + w[2] * (c2[1] - c0[1]);
+    bb = c0[2] + w[1] * (c1[2] - c0[2]) + w[2] * (c2[2] - c0[2]);
+  }
   rgb[i * 3 + 0] = rs_byte(br, I);
   rgb[i * 3 + 1] = rs_byte(bg, I);
   rgb[i * 3 + 2] = rs_byte(bb, I);
 }
 
+// COLORS: the pixel's own point's colour, point_rgb (P,3), or (F,P,3) when col_per_frame (frame_pixels = H * W), unlit
+template <bool COLORS>
 __global__ void __launch_bounds__(256) render_shade_points_kernel(const int* __restrict__ prim_id, long n, int prim_base, int P, int r, int g, int b,
-                                                                  unsigned char* __restrict__ rgb) {
+                                                                  unsigned char* __restrict__ rgb, const float* __restrict__ point_rgb, int col_per_frame,
+                                                                  long frame_pixels) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int id = prim_id[i];
   if (id < prim_base || id - prim_base >= P) return;
+  if constexpr (COLORS) {
+    const float* c = point_rgb + ((col_per_frame ? (i / frame_pixels) * P : 0L) + (id - prim_base)) * 3;
+    rgb[i * 3 + 0] = rs_byte(c[0], 1.0f);
+    rgb[i * 3 + 1] = rs_byte(c[1], 1.0f);
+    rgb[i * 3 + 2] = rs_byte(c[2], 1.0f);
+    return;
+  }
   rgb[i * 3 + 0] = (unsigned char)r;
   rgb[i * 3 + 1] = (unsigned char)g;
   rgb[i * 3 + 2] = (unsigned char)b;
+}
+
+// ---- composite and resolve ---------------------------------------------------------------------------------------------------
+constexpr int RS_MAX_ITEMS = 64;
+constexpr int RS_MAX_LAYERS = 8;
+
+struct RsItems {
+  int base[RS_MAX_ITEMS], count[RS_MAX_ITEMS];
+  float alpha[RS_MAX_ITEMS];
+  int n;
+};
+
+// one thread per pixel of (F, H, W): C = bg, then the K layers back to front, C = a byte / 255 + (1 - a) C where the layer's id belongs
+// to an item of alpha a; a layer whose id is negative or belongs to no item leaves C as it is.  n = F * H * W.
+__global__ void __launch_bounds__(256) render_composite_kernel(const unsigned char* __restrict__ layer_rgb, const int* __restrict__ layer_id, int K, long n,
+                                                               RsItems items, float bg_r, float bg_g, float bg_b, unsigned char* __restrict__ rgb) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float c[3] = {bg_r, bg_g, bg_b};
+  for (int k = K - 1; k >= 0; --k) {
+    const int id = layer_id[(long)k * n + i];
+    float a = 0.0f;
+    bool hit = false;
+    for (int j = 0; j < items.n; ++j)
+      if (id >= items.base[j] && id - items.base[j] < items.count[j]) a = items.alpha[j], hit = true;
+    if (!hit) continue;
+    const unsigned char* p = layer_rgb + ((long)k * n + i) * 3;
+    for (int ch = 0; ch < 3; ++ch) c[ch] = a * ((float)p[ch] / 255.0f) + (1.0f - a) * c[ch];
+  }
+  for (int ch = 0; ch < 3; ++ch) rgb[i * 3 + ch] = rs_byte(c[ch], 1.0f);
+}
+
+// one thread per output pixel of (F, H, W): the rounded mean of its s x s block of in (F, s H, s W, 3), in integers
+__global__ void __launch_bounds__(256) render_resolve_kernel(const unsigned char* __restrict__ in, int F, int H, int W, int s, unsigned char* __restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)F * H * W) return;
+  const int px = (int)(i % W), py = (int)((i / W) % H);
+  const long f = i / ((long)W * H);
+  const long row = (long)s * W * 3;
+  const unsigned char* p = in + (f * s * H + (long)py * s) * row + (long)px * s * 3;
+  int sum[3] = {0, 0, 0};
+  for (int y = 0; y < s; ++y)
+    for (int x = 0; x < s; ++x)
+      for (int ch = 0; ch < 3; ++ch) sum[ch] += p[y * row + x * 3 + ch];
+  const int nn = s * s;
+  for (int ch = 0; ch < 3; ++ch) out[i * 3 + ch] = (unsigned char)((sum[ch] + nn / 2) / nn);
 }

@@ -9,6 +9,7 @@
 #include "tamf_raster.h"
 
 static_assert(TAMF_RENDER_MAX_LIGHTS == RS_MAX_LIGHTS, "the header's light count is the kernels'");
+static_assert(TAMF_RENDER_MAX_ITEMS == RS_MAX_ITEMS && TAMF_RENDER_MAX_LAYERS == RS_MAX_LAYERS, "the header's composite limits are the kernels'");
 
 static thread_local std::string g_render_error;
 
@@ -80,41 +81,73 @@ extern "C" int tamf_render_clear(float* depth, int32_t* prim_id, int32_t F, int3
   return launched();
 }
 
-extern "C" int tamf_render_raster(const int32_t* xy, const float* pos_cam, const int32_t* faces, int32_t F, int32_t V, int32_t Nf, int32_t H,
-                                  int32_t W, int32_t prim_base, float* depth, int32_t* prim_id, void* stream) {
+// floor: both null (the plain pass) or both given (a peel pass)
+template <bool FLOOR>
+static int raster(const int32_t* xy, const float* pos_cam, const int32_t* faces, int32_t F, int32_t V, int32_t Nf, int32_t H, int32_t W, int32_t prim_base,
+                  const float* floor_depth, const int32_t* floor_id, float* depth, int32_t* prim_id, void* stream) {
   if (!xy || !pos_cam || !faces || !depth || !prim_id) return fail(TAMF_ERR_INVALID, "null argument: xy, pos_cam, faces, depth and prim_id are required");
+  if (FLOOR && (!floor_depth || !floor_id)) return fail(TAMF_ERR_INVALID, "null argument: floor_depth and floor_id are required");
+  if (FLOOR && (floor_depth == depth || floor_id == prim_id)) return fail(TAMF_ERR_INVALID, "the floor buffers must not be the buffers drawn into");
   std::string bad = bad_image(F, H, W);
   if (bad.empty()) bad = bad_prims(F, V, Nf, prim_base);
   if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
-  hipLaunchKernelGGL(render_raster_kernel, tiles(F, H, W), dim3(RS_NT), 0, (hipStream_t)stream, (const int*)xy, pos_cam, (const int*)faces, Nf, V,
-                     W, H, prim_base, depth, (int*)prim_id);
+  hipLaunchKernelGGL(render_raster_kernel<FLOOR>, tiles(F, H, W), dim3(RS_NT), 0, (hipStream_t)stream, (const int*)xy, pos_cam, (const int*)faces, Nf, V,
+                     W, H, prim_base, depth, (int*)prim_id, floor_depth, (const int*)floor_id);
   return launched();
 }
 
-extern "C" int tamf_render_points(const int32_t* xy, const float* pos_cam, int32_t F, int32_t P, int32_t H, int32_t W, int32_t point_size,
-                                  int32_t prim_base, float* depth, int32_t* prim_id, void* stream) {
+extern "C" int tamf_render_raster(const int32_t* xy, const float* pos_cam, const int32_t* faces, int32_t F, int32_t V, int32_t Nf, int32_t H,
+                                  int32_t W, int32_t prim_base, float* depth, int32_t* prim_id, void* stream) {
+  return raster<false>(xy, pos_cam, faces, F, V, Nf, H, W, prim_base, nullptr, nullptr, depth, prim_id, stream);
+}
+
+extern "C" int tamf_render_raster_behind(const int32_t* xy, const float* pos_cam, const int32_t* faces, int32_t F, int32_t V, int32_t Nf, int32_t H,
+                                         int32_t W, int32_t prim_base, const float* floor_depth, const int32_t* floor_id, float* depth,
+                                         int32_t* prim_id, void* stream) {
+  return raster<true>(xy, pos_cam, faces, F, V, Nf, H, W, prim_base, floor_depth, floor_id, depth, prim_id, stream);
+}
+
+template <bool FLOOR>
+static int points(const int32_t* xy, const float* pos_cam, int32_t F, int32_t P, int32_t H, int32_t W, int32_t point_size, int32_t prim_base,
+                  const float* floor_depth, const int32_t* floor_id, float* depth, int32_t* prim_id, void* stream) {
   if (!xy || !pos_cam || !depth || !prim_id) return fail(TAMF_ERR_INVALID, "null argument: xy, pos_cam, depth and prim_id are required");
+  if (FLOOR && (!floor_depth || !floor_id)) return fail(TAMF_ERR_INVALID, "null argument: floor_depth and floor_id are required");
+  if (FLOOR && (floor_depth == depth || floor_id == prim_id)) return fail(TAMF_ERR_INVALID, "the floor buffers must not be the buffers drawn into");
   std::string bad = bad_image(F, H, W);
   if (bad.empty()) bad = bad_prims(F, P, P, prim_base);
   if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
   if (point_size < 1 || point_size > TAMF_RENDER_MAX_POINT_SIZE || point_size % 2 == 0)
     return fail(TAMF_ERR_INVALID, "point_size must be odd and lie in [1, " + std::to_string(TAMF_RENDER_MAX_POINT_SIZE) + "], got " + std::to_string(point_size));
-  hipLaunchKernelGGL(render_points_kernel, tiles(F, H, W), dim3(RS_NT), 0, (hipStream_t)stream, (const int*)xy, pos_cam, P, W, H, point_size / 2,
-                     prim_base, depth, (int*)prim_id);
+  hipLaunchKernelGGL(render_points_kernel<FLOOR>, tiles(F, H, W), dim3(RS_NT), 0, (hipStream_t)stream, (const int*)xy, pos_cam, P, W, H, point_size / 2,
+                     prim_base, depth, (int*)prim_id, floor_depth, (const int*)floor_id);
   return launched();
 }
 
-extern "C" int tamf_render_shade_mesh(const int32_t* prim_id, const int32_t* xy, const float* pos_cam, const float* normals, const int32_t* faces,
-                                      int32_t F, int32_t V, int32_t Nf, int32_t H, int32_t W, int32_t prim_base, const float* base_rgb, float ambient,
-                                      const float* lights, int32_t L, uint8_t* rgb, void* stream) {
-  if (!prim_id || !xy || !pos_cam || !faces || !base_rgb || !rgb)
-    return fail(TAMF_ERR_INVALID, "null argument: prim_id, xy, pos_cam, faces, base_rgb and rgb are required");
+extern "C" int tamf_render_points(const int32_t* xy, const float* pos_cam, int32_t F, int32_t P, int32_t H, int32_t W, int32_t point_size,
+                                  int32_t prim_base, float* depth, int32_t* prim_id, void* stream) {
+  return points<false>(xy, pos_cam, F, P, H, W, point_size, prim_base, nullptr, nullptr, depth, prim_id, stream);
+}
+
+extern "C" int tamf_render_points_behind(const int32_t* xy, const float* pos_cam, int32_t F, int32_t P, int32_t H, int32_t W, int32_t point_size,
+                                         int32_t prim_base, const float* floor_depth, const int32_t* floor_id, float* depth, int32_t* prim_id,
+                                         void* stream) {
+  return points<true>(xy, pos_cam, F, P, H, W, point_size, prim_base, floor_depth, floor_id, depth, prim_id, stream);
+}
+
+// base_rgb: 3 HOST floats (the plain pass); vertex_rgb: device colours (the colour pass).  Exactly one of the two.
+template <bool COLORS>
+static int shade_mesh(const int32_t* prim_id, const int32_t* xy, const float* pos_cam, const float* normals, const int32_t* faces, int32_t F, int32_t V,
+                      int32_t Nf, int32_t H, int32_t W, int32_t prim_base, const float* base_rgb, const float* vertex_rgb, int32_t col_per_frame,
+                      float ambient, const float* lights, int32_t L, uint8_t* rgb, void* stream) {
+  if (!prim_id || !xy || !pos_cam || !faces || !(COLORS ? vertex_rgb : base_rgb) || !rgb)
+    return fail(TAMF_ERR_INVALID, COLORS ? "null argument: prim_id, xy, pos_cam, faces, vertex_rgb and rgb are required"
+                                         : "null argument: prim_id, xy, pos_cam, faces, base_rgb and rgb are required");
   if (L < 0 || L > RS_MAX_LIGHTS || (L > 0 && !lights))
     return fail(TAMF_ERR_INVALID, "L outside [0, " + std::to_string(RS_MAX_LIGHTS) + "], or lights null with L > 0 (L = " + std::to_string(L) + ")");
   std::string bad = bad_image(F, H, W);
   if (bad.empty()) bad = bad_prims(F, V, Nf, prim_base);
   if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
-  if (!finite3(base_rgb) || !std::isfinite(ambient)) return fail(TAMF_ERR_INVALID, "non-finite base colour or ambient term");
+  if ((!COLORS && !finite3(base_rgb)) || !std::isfinite(ambient)) return fail(TAMF_ERR_INVALID, "non-finite base colour or ambient term");
   RsLights Ls = {};
   Ls.ambient = ambient;
   Ls.n = L;
@@ -124,9 +157,22 @@ extern "C" int tamf_render_shade_mesh(const int32_t* prim_id, const int32_t* xy,
     Ls.strength[l] = lights[4 * l + 3];
   }
   const long n = (long)F * H * W;
-  hipLaunchKernelGGL(render_shade_mesh_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, (const int*)prim_id, (const int*)xy, pos_cam, normals,
-                     (const int*)faces, Nf, V, F, W, H, prim_base, base_rgb[0], base_rgb[1], base_rgb[2], Ls, rgb);
+  hipLaunchKernelGGL(render_shade_mesh_kernel<COLORS>, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, (const int*)prim_id, (const int*)xy, pos_cam, normals,
+                     (const int*)faces, Nf, V, F, W, H, prim_base, COLORS ? 0.0f : base_rgb[0], COLORS ? 0.0f : base_rgb[1], COLORS ? 0.0f : base_rgb[2], Ls,
+                     rgb, vertex_rgb, col_per_frame ? 1 : 0);
   return launched();
+}
+
+extern "C" int tamf_render_shade_mesh(const int32_t* prim_id, const int32_t* xy, const float* pos_cam, const float* normals, const int32_t* faces,
+                                      int32_t F, int32_t V, int32_t Nf, int32_t H, int32_t W, int32_t prim_base, const float* base_rgb, float ambient,
+                                      const float* lights, int32_t L, uint8_t* rgb, void* stream) {
+  return shade_mesh<false>(prim_id, xy, pos_cam, normals, faces, F, V, Nf, H, W, prim_base, base_rgb, nullptr, 0, ambient, lights, L, rgb, stream);
+}
+
+extern "C" int tamf_render_shade_mesh_colors(const int32_t* prim_id, const int32_t* xy, const float* pos_cam, const float* normals, const int32_t* faces,
+                                             int32_t F, int32_t V, int32_t Nf, int32_t H, int32_t W, int32_t prim_base, const float* vertex_rgb,
+                                             int32_t per_frame, float ambient, const float* lights, int32_t L, uint8_t* rgb, void* stream) {
+  return shade_mesh<true>(prim_id, xy, pos_cam, normals, faces, F, V, Nf, H, W, prim_base, nullptr, vertex_rgb, per_frame, ambient, lights, L, rgb, stream);
 }
 
 extern "C" int tamf_render_shade_points(const int32_t* prim_id, int32_t F, int32_t H, int32_t W, int32_t prim_base, int32_t P, const float* base_rgb,
@@ -137,8 +183,20 @@ extern "C" int tamf_render_shade_points(const int32_t* prim_id, int32_t F, int32
   if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
   if (!finite3(base_rgb)) return fail(TAMF_ERR_INVALID, "non-finite base colour");
   const long n = (long)F * H * W;
-  hipLaunchKernelGGL(render_shade_points_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, (const int*)prim_id, n, prim_base, P,
-                     to_byte(base_rgb[0]), to_byte(base_rgb[1]), to_byte(base_rgb[2]), rgb);
+  hipLaunchKernelGGL(render_shade_points_kernel<false>, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, (const int*)prim_id, n, prim_base, P,
+                     to_byte(base_rgb[0]), to_byte(base_rgb[1]), to_byte(base_rgb[2]), rgb, (const float*)nullptr, 0, (long)H * W);
+  return launched();
+}
+
+extern "C" int tamf_render_shade_points_colors(const int32_t* prim_id, int32_t F, int32_t H, int32_t W, int32_t prim_base, int32_t P,
+                                               const float* point_rgb, int32_t per_frame, uint8_t* rgb, void* stream) {
+  if (!prim_id || !point_rgb || !rgb) return fail(TAMF_ERR_INVALID, "null argument: prim_id, point_rgb and rgb are required");
+  std::string bad = bad_image(F, H, W);
+  if (bad.empty()) bad = bad_prims(F, P, P, prim_base);
+  if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
+  const long n = (long)F * H * W;
+  hipLaunchKernelGGL(render_shade_points_kernel<true>, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, (const int*)prim_id, n, prim_base, P, 0, 0, 0, rgb,
+                     point_rgb, per_frame ? 1 : 0, (long)H * W);
   return launched();
 }
 
@@ -150,5 +208,50 @@ extern "C" int tamf_render_fill(const int32_t* prim_id, int32_t F, int32_t H, in
   const long n = (long)F * H * W;
   hipLaunchKernelGGL(render_fill_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, (const int*)prim_id, rgb, n, to_byte(bg_rgb[0]),
                      to_byte(bg_rgb[1]), to_byte(bg_rgb[2]));
+  return launched();
+}
+
+extern "C" int tamf_render_composite(const uint8_t* layer_rgb, const int32_t* layer_id, int32_t K, int32_t F, int32_t H, int32_t W,
+                                     const int32_t* item_base, const int32_t* item_count, const float* item_alpha, int32_t n_items,
+                                     const float* bg_rgb, uint8_t* rgb, void* stream) {
+  if (!layer_rgb || !layer_id || !item_base || !item_count || !item_alpha || !bg_rgb || !rgb)
+    return fail(TAMF_ERR_INVALID, "null argument: layer_rgb, layer_id, the item table, bg_rgb and rgb are required");
+  if (K < 1 || K > RS_MAX_LAYERS) return fail(TAMF_ERR_INVALID, "K outside [1, " + std::to_string(RS_MAX_LAYERS) + "], got " + std::to_string(K));
+  if (n_items < 1 || n_items > RS_MAX_ITEMS)
+    return fail(TAMF_ERR_INVALID, "the item table holds 1 to " + std::to_string(RS_MAX_ITEMS) + " rows, got " + std::to_string(n_items));
+  const std::string bad = bad_image(F, H, W);
+  if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
+  if (!finite3(bg_rgb)) return fail(TAMF_ERR_INVALID, "non-finite background colour");
+  if (rgb == layer_rgb) return fail(TAMF_ERR_INVALID, "rgb must not be the layers' buffer");
+  RsItems items = {};
+  items.n = n_items;
+  long end = 0;  // rows ascending and disjoint: an id belongs to one row at most
+  for (int i = 0; i < n_items; ++i) {
+    const std::string row = "item " + std::to_string(i) + ": ";
+    if (item_base[i] < 0 || item_count[i] < 1 || (long)item_base[i] + item_count[i] > RN_INT_MAX)
+      return fail(TAMF_ERR_INVALID, row + "prim_base < 0, count < 1 or prim_base + count above 2^31 - 1");
+    if (item_base[i] < end) return fail(TAMF_ERR_INVALID, row + "the rows must ascend in prim_base and must not overlap");
+    if (!(item_alpha[i] > 0.0f && item_alpha[i] <= 1.0f)) return fail(TAMF_ERR_INVALID, row + "alpha must lie in (0, 1]");
+    end = (long)item_base[i] + item_count[i];
+    items.base[i] = item_base[i], items.count[i] = item_count[i], items.alpha[i] = item_alpha[i];
+  }
+  const long n = (long)F * H * W;
+  const auto clamp01 = [](float c) { return std::fmin(std::fmax(c, 0.0f), 1.0f); };
+  hipLaunchKernelGGL(render_composite_kernel, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, layer_rgb, (const int*)layer_id, K, n, items,
+                     clamp01(bg_rgb[0]), clamp01(bg_rgb[1]), clamp01(bg_rgb[2]), rgb);
+  return launched();
+}
+
+extern "C" int tamf_render_resolve(const uint8_t* rgb_in, int32_t F, int32_t H, int32_t W, int32_t s, uint8_t* rgb, void* stream) {
+  if (!rgb_in || !rgb) return fail(TAMF_ERR_INVALID, "null argument: rgb_in and rgb are required");
+  if (s < 2 || s > 4) return fail(TAMF_ERR_INVALID, "s must be 2, 3 or 4, got " + std::to_string(s));
+  if (rgb_in == rgb) return fail(TAMF_ERR_INVALID, "rgb must not be rgb_in");
+  std::string bad = bad_image(F, H, W);
+  if (bad.empty() && ((long)s * W > TAMF_RENDER_MAX_SIDE || (long)s * H > TAMF_RENDER_MAX_SIDE))
+    bad = "s * W and s * H must not exceed " + std::to_string(TAMF_RENDER_MAX_SIDE) + " (s = " + std::to_string(s) + ", H = " + std::to_string(H) +
+          ", W = " + std::to_string(W) + ")";
+  if (bad.empty()) bad = bad_image(F, s * H, s * W);
+  if (!bad.empty()) return fail(TAMF_ERR_INVALID, bad);
+  hipLaunchKernelGGL(render_resolve_kernel, dim3(blocks((long)F * H * W)), dim3(256), 0, (hipStream_t)stream, rgb_in, F, H, W, s, rgb);
   return launched();
 }

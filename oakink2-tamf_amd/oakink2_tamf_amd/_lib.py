@@ -13,7 +13,8 @@ that description:
   REFINETRAIN csrc/tamf_refinetrain.hip -> libtamf_refinetrain.so (include/tamf_refinetrain.h: the SegmentRefineModel training step - forward, backward)
   MDMTRAIN csrc/tamf_mdmtrain.hip -> libtamf_mdmtrain.so (include/tamf_mdmtrain.h: the InterationSegmentMDM training step - forward, backward)
   OPTIM    csrc/tamf_optim.hip -> libtamf_optim.so (include/tamf_optim.h: per-parameter gradient clipping + AdamW over a tensor table)
-  RENDER   csrc/tamf_render.hip -> libtamf_render.so (include/tamf_render.h: projection, triangle / point rasteriser, Lambert shading)
+  RENDER   csrc/tamf_render.hip -> libtamf_render.so (include/tamf_render.h: projection, triangle / point rasteriser, Lambert shading,
+           depth peeling, composite, supersampling resolve)
 POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
 score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
 ENCTRAIN, REFINETRAIN and MDMTRAIN share tamf_train_host.h (the table of bound tensors, the context base, the call checks, the
@@ -93,7 +94,8 @@ OPTIM_EXPORTS = [  # include/tamf_optim.h: what libtamf_optim.so exports
 ]
 RENDER_EXPORTS = [  # include/tamf_render.h: what libtamf_render.so exports
     "tamf_render_last_error", "tamf_render_project", "tamf_render_clear", "tamf_render_raster", "tamf_render_points", "tamf_render_shade_mesh",
-    "tamf_render_shade_points", "tamf_render_fill",
+    "tamf_render_shade_points", "tamf_render_fill", "tamf_render_raster_behind", "tamf_render_points_behind", "tamf_render_shade_mesh_colors",
+    "tamf_render_shade_points_colors", "tamf_render_composite", "tamf_render_resolve",
 ]
 
 
@@ -312,7 +314,9 @@ OPTIM = Library("libtamf_optim", "tamf_optim.hip", ("tamf_optim.h", "tamf_hip.h"
                 kernels=("_Z18optim_sumsq_kernel", "_Z19optim_update_kernel", "_Z17optim_norm_kernel"))
 RENDER = Library("libtamf_render", "tamf_render.hip", ("tamf_render.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
                  (Output("libtamf_render.so", (), RENDER_EXPORTS),),
-                 kernels=("_Z21render_project_kernel", "_Z20render_raster_kernel", "_Z20render_points_kernel", "_Z24render_shade_mesh_kernel"))
+                 kernels=("_Z21render_project_kernel", "_Z20render_raster_kernelILb0EE", "_Z20render_raster_kernelILb1EE", "_Z20render_points_kernelILb0EE",
+                          "_Z20render_points_kernelILb1EE", "_Z24render_shade_mesh_kernelILb0EE", "_Z24render_shade_mesh_kernelILb1EE",
+                          "_Z23render_composite_kernel", "_Z21render_resolve_kernel"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)

@@ -7,12 +7,23 @@ an Open3D window and dev_fn/util/vis_pyrender_util.py renders through OpenGL; a 
         --debug.sample_refine_filepath common/sample_refine/main/sample/test/arch_mdm_l__0399 --out_dir render/test/arch_mdm_l__0399 \
         [--data.obj_model_loader pkg.mod:load_obj] [--with_gt --mano.factory pkg.mod:make_mano] [--render.width 512] [--render.height 512]
         [--render.every 1] [--render.sheet_cols 8] [--render.point_size 3] [--max_clips N] [--device cuda:0] [--out_json index.json] [--dry_run]
+        [--render.contact_map [--render.contact_far_mm 30]] [--render.obj_alpha 1.0] [--render.layers K] [--render.ssaa 1]
+        [--render.apng [--render.apng_fps 10]]
 
 The `--data.*`, `--debug.sample_refine_filepath` and `--mano.*` names of compute_score_cr.py (launch/_score_common.py), and:
   --data.obj_model_loader module:function   function(obj_id) -> (verts, faces), as compute_score_siv.py takes it: the objects are drawn
                                             as meshes; without it as the splats of their `obj_pointcloud`
   --with_gt                                 a second panel beside the refined one: the ground-truth hand (pose decode -> MANO) in a second
                                             colour with the same objects and camera; needs --mano.factory and is refused without it
+  --render.contact_map                      every hand panel's vertices are coloured by their distance to the clip's objects
+                                            (contact.merged_h2o_dist against `obj_pointcloud` moved along `obj_traj`): the contact colour at
+                                            5 mm (the CR score's threshold) and nearer, the hand's own colour from --render.contact_far_mm
+                                            (a display default) on; refused when the item carries no point cloud.  On the hand only.
+  --render.obj_alpha A                      the objects are drawn see-through with alpha A in (0, 1]: the fingers behind them show
+  --render.layers K                         depth layers peeled per pixel, 1 .. 8 (default 1, and 4 when obj_alpha < 1)
+  --render.ssaa S                           S x S sub-samples a pixel, 1 .. 4 (default 1)
+  --render.apng                             also clip.apng beside sheet.png: the drawn frames as one animated PNG at --render.apng_fps
+                                            (default 10, the dataset's target_fps)
 Per clip: the refined hand is the save dict's `verts` over its `faces` (the --mano.factory tuple's closed faces when the save dict
 holds none), every object of `obj_list` moves along the item's `obj_traj`, frames 0, every, 2 every, ... of the first `len` frames are
 drawn from ONE camera fitted to everything in them (render.look_at_camera).  Output under
@@ -37,6 +48,10 @@ PROG = "render_samples"
 HAND_COLOR, GT_HAND_COLOR = (0.91, 0.72, 0.60), (0.45, 0.65, 0.90)
 OBJ_COLORS = ((0.55, 0.80, 0.45), (0.90, 0.55, 0.35), (0.70, 0.55, 0.85), (0.85, 0.80, 0.40))
 RENDER_DEFAULTS = {"width": 512, "height": 512, "every": 1, "sheet_cols": 8, "point_size": 3}
+CONTACT_COLOR = (1.0, 0.1, 0.05)
+CONTACT_NEAR = 0.005  # metres: the contact threshold of the CR score
+# what draws the picture differently; kept apart from cfg["render"], which stays the five sizes above
+DISPLAY_DEFAULTS = {"contact_map": False, "contact_far_mm": 30.0, "obj_alpha": 1.0, "layers": 1, "ssaa": 1, "apng": False, "apng_fps": 10}
 
 
 def parse_args(argv):
@@ -45,6 +60,13 @@ def parse_args(argv):
                     help="module:function, function(obj_id) -> (verts, faces): draw the objects as meshes")
     for key, default in RENDER_DEFAULTS.items():
         ap.add_argument("--render." + key, dest="render__" + key, type=int, default=default)
+    ap.add_argument("--render.contact_map", dest="display__contact_map", action="store_true", help="colour the hand by its distance to the objects")
+    ap.add_argument("--render.contact_far_mm", dest="display__contact_far_mm", type=float, default=DISPLAY_DEFAULTS["contact_far_mm"])
+    ap.add_argument("--render.obj_alpha", dest="display__obj_alpha", type=float, default=DISPLAY_DEFAULTS["obj_alpha"])
+    ap.add_argument("--render.layers", dest="display__layers", type=int, default=None, help="peeled depth layers (default 1; 4 when obj_alpha < 1)")
+    ap.add_argument("--render.ssaa", dest="display__ssaa", type=int, default=DISPLAY_DEFAULTS["ssaa"])
+    ap.add_argument("--render.apng", dest="display__apng", action="store_true", help="also write clip.apng")
+    ap.add_argument("--render.apng_fps", dest="display__apng_fps", type=int, default=DISPLAY_DEFAULTS["apng_fps"])
     ap.add_argument("--out_dir", default=os.path.join("common", "render_samples", "main"))
     ap.add_argument("--max_clips", type=int, default=None, help="render the first N clips only")
     ap.add_argument("--with_gt", action="store_true", help="second panel: the ground-truth hand (needs --mano.factory)")
@@ -62,7 +84,23 @@ def parse_args(argv):
         ap.error("--max_clips must be at least 1")
     if a.with_gt and not cfg["mano"]["factory"]:
         ap.error("--with_gt draws the ground-truth hand through MANO: pass --mano.factory module:function")
+    d = {key: getattr(a, "display__" + key) for key in DISPLAY_DEFAULTS}
+    if not 0.0 < d["obj_alpha"] <= 1.0:
+        ap.error("--render.obj_alpha must lie in (0, 1]")
+    if d["layers"] is None:
+        d["layers"] = 4 if d["obj_alpha"] < 1.0 else 1
+    if not 1 <= d["layers"] <= 8:
+        ap.error("--render.layers must lie in [1, 8]")
+    if not 1 <= d["ssaa"] <= 4 or d["ssaa"] * max(r["width"], r["height"]) > 4096:
+        ap.error("--render.ssaa must lie in [1, 4], with ssaa * width and ssaa * height at most 4096")
+    if d["ssaa"] * r["point_size"] + (1 - d["ssaa"] * r["point_size"] % 2) > 15:
+        ap.error("--render.ssaa * --render.point_size (made odd) must not exceed 15")
+    if not d["contact_far_mm"] > 1e3 * CONTACT_NEAR:  # (false for NaN)
+        ap.error("--render.contact_far_mm must exceed the contact threshold of %g mm" % (1e3 * CONTACT_NEAR))
+    if not 1 <= d["apng_fps"] <= 1000:
+        ap.error("--render.apng_fps must lie in [1, 1000]")
     cfg["render"] = r
+    cfg["display"] = d
     cfg["runtime"].update(out_dir=os.path.abspath(a.out_dir), max_clips=a.max_clips, with_gt=a.with_gt)
     return cfg
 
@@ -79,10 +117,13 @@ def render_clip(item, hands, faces, cfg, device):
     """hands: [(verts (T, 778, 3), colour)], one panel each -> (frames, images (n, H, panels * W, 3) uint8 numpy)"""
     from .. import render as R
 
-    r = cfg["render"]
+    r, d = cfg["render"], cfg["display"]
     frames = drawn_frames(item["len"], r["every"])
     if not frames:
         return frames, None
+    if d["contact_map"] and "obj_pointcloud" not in item:
+        raise SystemExit(f"--render.contact_map: clip {tuple(item['info'])} carries no obj_pointcloud to measure the hand against "
+                         "(pass --data.obj_pointcloud_prefix)")
     poses = [R.tslrot6d_to_matrix(np.asarray(item["obj_traj"])[k]) for k in range(len(item["obj_list"]))]
     meshes = "obj_verts" in item
     shapes = [np.asarray(item["obj_verts"][k] if meshes else item["obj_pointcloud"][k], np.float64) for k in range(len(item["obj_list"]))]
@@ -93,15 +134,33 @@ def render_clip(item, hands, faces, cfg, device):
     panels = []
     for verts, colour in hands:
         rd = R.HipRenderer(r["width"], r["height"], device)
-        rd.add_mesh(np.asarray(verts, np.float32)[frames], faces, color=colour, smooth=True, name="hand")
+        hand = np.asarray(verts, np.float32)[frames]
+        rd.add_mesh(hand, faces, color=colour, smooth=True, name="hand", vertex_colors=contact_map(item, hand, frames, colour, d, device) if d["contact_map"] else None)
         for k, (m, s) in enumerate(zip(poses, shapes)):
             colour_k = OBJ_COLORS[k % len(OBJ_COLORS)]
             if meshes:
-                rd.add_mesh(s, item["obj_faces"][k], color=colour_k, pose=m[frames], name=str(item["obj_list"][k]))
+                rd.add_mesh(s, item["obj_faces"][k], color=colour_k, pose=m[frames], name=str(item["obj_list"][k]), alpha=d["obj_alpha"])
             else:
-                rd.add_points(s, color=colour_k, pose=m[frames], point_size=r["point_size"], name=str(item["obj_list"][k]))
-        panels.append(rd.render(cam)[0].cpu().numpy())
+                rd.add_points(s, color=colour_k, pose=m[frames], point_size=r["point_size"], name=str(item["obj_list"][k]), alpha=d["obj_alpha"])
+        panels.append(rd.render(cam, layers=d["layers"], ssaa=d["ssaa"])[0].cpu().numpy())
     return frames, np.concatenate(panels, axis=2)
+
+
+def contact_map(item, hand, frames, colour, d, device):
+    """the heat map of one hand panel: hand (n, V, 3) at the drawn frames -> colours (n, V, 3) on the device, from the distance of every
+    vertex to the nearest point of any of the clip's objects (contact.merged_h2o_dist, the refiner's feature)"""
+    import torch
+
+    from .. import render as R
+    from ..contact import merged_h2o_dist
+
+    nobj = len(item["obj_list"])
+    traj = np.stack([np.asarray(item["obj_traj"])[k][frames] for k in range(nobj)]).astype(np.float32)  # (nobj, n, 9)
+    clouds = np.stack([np.asarray(item["obj_pointcloud"][k], np.float32) for k in range(nobj)])  # (nobj, P, 3)
+    with torch.no_grad():
+        dist = merged_h2o_dist(torch.from_numpy(np.ascontiguousarray(hand))[None].to(device), torch.from_numpy(traj)[None].to(device),
+                               torch.from_numpy(clouds)[None].to(device))[0]
+    return R.contact_colors(dist, colour, hot=CONTACT_COLOR, near=CONTACT_NEAR, far=1e-3 * d["contact_far_mm"])
 
 
 def main(argv=None) -> int:
@@ -116,7 +175,7 @@ def main(argv=None) -> int:
     if rt["dry_run"]:
         print(json.dumps({"n_clips": len(pairs), "pairs": C.pair_listing(pairs), "sample_refine_filepath": cfg["debug"]["sample_refine_filepath"],
                           "obj_model_loader": cfg["data"]["obj_model_loader"], "out_dir": rt["out_dir"], "render": cfg["render"],
-                          "with_gt": rt["with_gt"]}))
+                          "display": cfg["display"], "with_gt": rt["with_gt"]}))
         return 0
     import torch
 
@@ -150,10 +209,15 @@ def main(argv=None) -> int:
                 entry["files"].append(name)
             R.write_png(os.path.join(out, "sheet.png"), R.contact_sheet(images[:: cfg["render"]["sheet_cols"]], cfg["render"]["sheet_cols"]))
             entry["sheet"] = "sheet.png"
+            if cfg["display"]["apng"]:
+                R.write_apng(os.path.join(out, "clip.apng"), images, cfg["display"]["apng_fps"])
+                entry["apng"] = "clip.apng"
         index.append(entry)
         print(f"{out} {len(frames)} frames")
     res = {"n_clips": len(index), "n_frames": sum(len(e["frames"]) for e in index), "out_dir": rt["out_dir"], "render": cfg["render"],
            "with_gt": rt["with_gt"], "clips": index}
+    if cfg["display"] != DISPLAY_DEFAULTS:
+        res["display"] = cfg["display"]
     print(f"n_frames {res['n_frames']}")
     if rt["out_json"]:
         C.write_json(rt["out_json"], res)

@@ -1,8 +1,11 @@
 """How long rendering a clip takes on the device (libtamf_render.so through render.HipRenderer): ms per 160-frame clip at 512 x 512 of a
 hand (1 554 faces, per-frame vertices, smooth shading) and two objects with per-frame poses - as meshes of 20 000 and 100 352 faces, and
-again as point clouds of 8 192 points each - plus the time of the rasteriser's launches alone.
+again as point clouds of 8 192 points each - plus the time of the rasteriser's launches alone.  The mesh clip is measured three ways in
+the same process: as it always was (one opaque layer), with the objects see-through and `--layers` (4) peeled layers, and with that and
+`--ssaa` (2) x (2) sub-samples a pixel; and the hand's peel pass (tamf_render_raster_behind) beside its plain raster pass.
 
-    python tools/render_bench.py [--frames 160] [--width 512] [--height 512] [--warmup 2] [--reps 5] [--out render_bench.json]
+    python tools/render_bench.py [--frames 160] [--width 512] [--height 512] [--warmup 2] [--reps 5] [--layers 4] [--ssaa 2] [--obj_alpha 0.4]
+                                 [--out render_bench.json]
 
 Times are device events around the enqueued work, ended by a synchronise, after warm-up passes of the same shapes; the median and the
 spread (min, max) over --reps are printed, one JSON line.  Needs a GPU: there is no fall-back, and a CPU run says nothing about speed.
@@ -76,6 +79,9 @@ def main(argv=None) -> int:
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--layers", type=int, default=4)
+    ap.add_argument("--ssaa", type=int, default=2)
+    ap.add_argument("--obj_alpha", type=float, default=0.4)
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
@@ -97,14 +103,14 @@ def main(argv=None) -> int:
     world = [hand.reshape(-1, 3)] + [np.asarray(c) + np.array([[-0.1, -0.1, -0.1], [0.1, 0.1, 0.1]]) for c in centres]
     cam = R.look_at_camera(np.concatenate(world), W, H)
 
-    def scene(as_points: bool):
+    def scene(as_points: bool, alpha: float = 1.0):
         rd = R.HipRenderer(W, H, a.device)
         rd.add_mesh(hand, hand_f, color=(0.91, 0.72, 0.60), smooth=True, name="hand")
         for k in range(2):
             if as_points:
-                rd.add_points(clouds[k], color=(0.55, 0.8, 0.45), pose=obj_pose[k], point_size=3)
+                rd.add_points(clouds[k], color=(0.55, 0.8, 0.45), pose=obj_pose[k], point_size=3, alpha=alpha)
             else:
-                rd.add_mesh(objects[k][0], objects[k][1], color=(0.55, 0.8, 0.45), pose=obj_pose[k])
+                rd.add_mesh(objects[k][0], objects[k][1], color=(0.55, 0.8, 0.45), pose=obj_pose[k], alpha=alpha)
         return rd
 
     res = {"frames": F, "width": W, "height": H, "device": torch.cuda.get_device_name(torch.device(a.device)), "warmup": a.warmup, "reps": a.reps,
@@ -115,6 +121,11 @@ def main(argv=None) -> int:
         res[label + "_clip"] = timed(lambda: rd.render(cam), a.warmup, a.reps)
         rgb, depth, prim = rd.render(cam)
         res[label + "_covered_share"] = float((prim >= 0).float().mean())
+    # the layered paths beside today's, same process, same scene with see-through objects
+    rd = scene(False, a.obj_alpha)
+    for label, kw in (("layers", dict(layers=a.layers)), ("layers_ssaa", dict(layers=a.layers, ssaa=a.ssaa))):
+        res["frames_per_chunk"]["meshes_" + label] = rd.frames_per_chunk(kw.get("layers", 1), kw.get("ssaa", 1))
+        res["meshes_" + label + "_clip"] = dict(timed(lambda: rd.render(cam, **kw), a.warmup, a.reps), **kw)
     # the rasteriser's launches alone, per mesh: projection kept outside the timed window
     lib = R._bind()
     cs = R.camera_struct(cam)
@@ -137,6 +148,13 @@ def main(argv=None) -> int:
             R._check(lib, lib.tamf_render_raster(P(xy), P(pos), P(fd), F, V, int(fd.shape[0]), H, W, 0, P(depth), P(prim), None))
 
         res["raster_" + label] = timed(raster, a.warmup, a.reps)
+        floor_d, floor_i = depth.clone(), prim.clone()  # the pass above left layer 0 in depth / prim
+
+        def behind():
+            R._check(lib, lib.tamf_render_clear(P(depth), P(prim), F, H, W, None))
+            R._check(lib, lib.tamf_render_raster_behind(P(xy), P(pos), P(fd), F, V, int(fd.shape[0]), H, W, 0, P(floor_d), P(floor_i), P(depth), P(prim), None))
+
+        res["raster_behind_" + label] = timed(behind, a.warmup, a.reps)
     line = json.dumps(res)
     print(line)
     if a.out:
