@@ -15,6 +15,8 @@ that description:
   OPTIM    csrc/tamf_optim.hip -> libtamf_optim.so (include/tamf_optim.h: per-parameter gradient clipping + AdamW over a tensor table)
   RENDER   csrc/tamf_render.hip -> libtamf_render.so (include/tamf_render.h: projection, triangle / point rasteriser, Lambert shading,
            depth peeling, composite, supersampling resolve)
+  SURFACE  csrc/tamf_surface.hip -> libtamf_surface.so (include/tamf_surface.h: the bit-defined surface sampler behind the object point
+           clouds - face areas, block scan with a fixed carry pass, Philox draw + binary search on the CDF)
 POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
 score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
 ENCTRAIN, REFINETRAIN and MDMTRAIN share tamf_train_host.h (the table of bound tensors, the context base, the call checks, the
@@ -46,6 +48,7 @@ REFINETRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_refinetrain.so")
 MDMTRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_mdmtrain.so")
 OPTIM_LIB_PATH = os.path.join(LIB_DIR, "libtamf_optim.so")
 RENDER_LIB_PATH = os.path.join(LIB_DIR, "libtamf_render.so")
+SURFACE_LIB_PATH = os.path.join(LIB_DIR, "libtamf_surface.so")
 
 EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_ctx_create", "tamf_ctx_resize", "tamf_ctx_destroy", "tamf_last_error", "tamf_load_weight", "tamf_finalize_weights",
@@ -96,6 +99,9 @@ RENDER_EXPORTS = [  # include/tamf_render.h: what libtamf_render.so exports
     "tamf_render_last_error", "tamf_render_project", "tamf_render_clear", "tamf_render_raster", "tamf_render_points", "tamf_render_shade_mesh",
     "tamf_render_shade_points", "tamf_render_fill", "tamf_render_raster_behind", "tamf_render_points_behind", "tamf_render_shade_mesh_colors",
     "tamf_render_shade_points_colors", "tamf_render_composite", "tamf_render_resolve",
+]
+SURFACE_EXPORTS = [  # include/tamf_surface.h: what libtamf_surface.so exports
+    "tamf_surface_last_error", "tamf_surface_workspace_bytes", "tamf_surface_sample",
 ]
 
 
@@ -317,6 +323,9 @@ RENDER = Library("libtamf_render", "tamf_render.hip", ("tamf_render.h", "tamf_hi
                  kernels=("_Z21render_project_kernel", "_Z20render_raster_kernelILb0EE", "_Z20render_raster_kernelILb1EE", "_Z20render_points_kernelILb0EE",
                           "_Z20render_points_kernelILb1EE", "_Z24render_shade_mesh_kernelILb0EE", "_Z24render_shade_mesh_kernelILb1EE",
                           "_Z23render_composite_kernel", "_Z21render_resolve_kernel"))
+SURFACE = Library("libtamf_surface", "tamf_surface.hip", ("tamf_surface.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
+                  (Output("libtamf_surface.so", ("-ffp-contract=off",), SURFACE_EXPORTS),),
+                  kernels=("_Z24surface_area_scan_kernel", "_Z20surface_carry_kernel", "_Z24surface_add_carry_kernel", "_Z21surface_sample_kernel"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)
@@ -325,11 +334,12 @@ REFINE_TRAINING = (REFINETRAIN,)  # the refiner's training step (model/segment_r
 DENOISER_TRAINING = (MDMTRAIN,)  # the denoiser's training step (model/interaction_segment_mdm_train.py); a group of its own for the same reason
 OPTIMISER = (OPTIM,)  # the optimiser step of the train / train_refine launchers (optim.py); a group of its own for the same reason
 RENDERING = (RENDER,)  # the offscreen renderer behind launch/render_samples.py (render.py); a group of its own for the same reason
+OBJECT_PREPROCESSING = (SURFACE,)  # the surface sampler behind launch/sample_object_points.py (surface.py); a group of its own for the same reason
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Every library, the sampler pair first, each only when ITS sources changed.  One library at a time.  Returns LIB_PATH."""
-    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING + OPTIMISER + RENDERING:
+    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING + OPTIMISER + RENDERING + OBJECT_PREPROCESSING:
         lib.build(force, verbose)
     return LIB_PATH
 
@@ -416,6 +426,11 @@ def load_optim() -> ctypes.CDLL:
 def load_render() -> ctypes.CDLL:
     """libtamf_render.so (include/tamf_render.h).  Independent of the other libraries."""
     return _load(RENDER, "libtamf_render.so")
+
+
+def load_surface() -> ctypes.CDLL:
+    """libtamf_surface.so (include/tamf_surface.h).  Independent of the other libraries."""
+    return _load(SURFACE, "libtamf_surface.so")
 
 
 def load_from(path: str) -> ctypes.CDLL:

@@ -7,6 +7,10 @@ The reference has no such script and does not say how the published embeddings w
   --color r,g,b   fills the colour channels of xyz-only clouds when the encoder takes 6 channels (required then)
   --pc_norm       centres the xyz on their centroid and scales by the largest norm (off by default)
   --seed          draws the FPS start indices from a CPU generator (default: index 0 everywhere)
+  --data.obj_mesh_prefix DIR   takes the clouds from mesh files instead of .npz files: DIR/<obj_id>.{obj,ply,stl} (or the single mesh file
+                  in DIR/<obj_id>/) is sampled in memory exactly as launch/sample_object_points.py writes it (`npoints` points,
+                  --sample.oversample 4, --sample.seed 0, --sample.scale 1.0, --sample.with_normals; key = FNV-1a 64 of the id), so the
+                  embedding equals, bit for bit, the one made from that launcher's file; --data.obj_pointcloud_prefix is not read then
 A cloud with more than `npoints` points is FPS-resampled to `npoints` (from the same start index); one with fewer is rejected."""
 from __future__ import annotations
 
@@ -30,7 +34,13 @@ def make_parser() -> argparse.ArgumentParser:
                     help="yaml with the encoder's fields (the reference's PointTransformer_8192point_2layer.yaml layout, or the fields "
                          "at top level); default: trans_dim 384, depth 12, 6 heads, 512 groups of 32, encoder_dims 256, point_dims 6, 8192 points")
     ap.add_argument("--data.obj_pointcloud_prefix", dest="prefix", default=DEFAULT_POINTCLOUD_PREFIX)
-    ap.add_argument("--obj_ids", default=None, help="comma-separated ids or ?(file:list.txt); default: every .npz under the prefix")
+    ap.add_argument("--data.obj_mesh_prefix", dest="mesh_prefix", default=None,
+                    help="sample the clouds from the mesh files of this directory (as sample_object_points does) instead of reading .npz files")
+    ap.add_argument("--sample.oversample", dest="sample_oversample", type=int, default=4)
+    ap.add_argument("--sample.seed", dest="sample_seed", type=int, default=0)
+    ap.add_argument("--sample.scale", dest="sample_scale", type=float, default=1.0)
+    ap.add_argument("--sample.with_normals", dest="sample_with_normals", action="store_true")
+    ap.add_argument("--obj_ids", default=None, help="comma-separated ids or ?(file:list.txt); default: every .npz (or mesh) under the prefix")
     ap.add_argument("--out_dir", default=DEFAULT_OUT_DIR)
     ap.add_argument("--color", default=None, help="r,g,b for xyz-only clouds")
     ap.add_argument("--pc_norm", action="store_true")
@@ -54,6 +64,29 @@ def load_cfg(path: Optional[str]) -> Dict[str, int]:
     if "npoints" in y:
         fields["npoints"] = y["npoints"]
     return make_cfg(fields)
+
+
+def list_mesh_work(prefix: str, obj_ids: Optional[List[str]], out_dir: str) -> List[Dict]:
+    """list_work over a directory of mesh files: `pointcloud` names the mesh the cloud is sampled from"""
+    from .sample_object_points import list_work as list_meshes
+
+    return [{"obj_id": w["obj_id"], "pointcloud": w["source"], "embedding": os.path.join(out_dir, f"{w['obj_id']}.pt")}
+            for w in list_meshes(prefix, obj_ids, out_dir, False)]
+
+
+def load_cloud(w: Dict, a, npoints: int) -> np.ndarray:
+    """the raw cloud of one work item: the .npz's "point", or - with --data.obj_mesh_prefix - the mesh sampled as sample_object_points does"""
+    if a.mesh_prefix is None:
+        with np.load(w["pointcloud"]) as z:
+            return z["point"]
+    from .. import mesh_io
+    from .sample_object_points import object_cloud, scaled
+
+    try:
+        v, f = mesh_io.read_mesh(w["pointcloud"])
+        return object_cloud(scaled(v, a.sample_scale), f, w["obj_id"], npoints, a.sample_oversample, a.sample_seed, a.sample_with_normals, a.device)["point"]
+    except ValueError as e:
+        raise SystemExit(f"embed_objects: {w['pointcloud']}: {e}")
 
 
 def list_work(prefix: str, obj_ids: Optional[List[str]], out_dir: str) -> List[Dict]:
@@ -107,7 +140,8 @@ def main(argv=None) -> int:
         color = [float(x) for x in a.color.split(",")]
         if len(color) != 3:
             raise SystemExit("embed_objects: --color takes r,g,b")
-    work = list_work(prefix, _str_list(a.obj_ids) if a.obj_ids is not None else None, out_dir)
+    ids = _str_list(a.obj_ids) if a.obj_ids is not None else None
+    work = list_work(prefix, ids, out_dir) if a.mesh_prefix is None else list_mesh_work(_abspath(a.mesh_prefix), ids, out_dir)
     if a.dry_run:
         import json
 
@@ -128,11 +162,10 @@ def main(argv=None) -> int:
         part = work[s: s + max(1, a.batch_size)]
         clouds, starts = [], []
         for w in part:
-            with np.load(w["pointcloud"]) as z:
-                try:
-                    p = prepare_cloud(z["point"], cfg["point_dims"], color, a.pc_norm)
-                except ValueError as e:
-                    raise SystemExit(f"embed_objects: {w['pointcloud']}: {e}")
+            try:
+                p = prepare_cloud(load_cloud(w, a, npoints), cfg["point_dims"], color, a.pc_norm)
+            except ValueError as e:
+                raise SystemExit(f"embed_objects: {w['pointcloud']}: {e}")
             if p.shape[0] < npoints:
                 raise SystemExit(f"embed_objects: {w['pointcloud']}: {p.shape[0]} points, the encoder takes {npoints}")
             start = int(torch.randint(0, npoints, (1,), generator=gen)) if gen is not None else 0

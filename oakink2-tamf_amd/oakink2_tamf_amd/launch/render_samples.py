@@ -13,6 +13,8 @@ an Open3D window and dev_fn/util/vis_pyrender_util.py renders through OpenGL; a 
 The `--data.*`, `--debug.sample_refine_filepath` and `--mano.*` names of compute_score_cr.py (launch/_score_common.py), and:
   --data.obj_model_loader module:function   function(obj_id) -> (verts, faces), as compute_score_siv.py takes it: the objects are drawn
                                             as meshes; without it as the splats of their `obj_pointcloud`
+  --data.obj_mesh_prefix DIR                the built-in loader in its place: mesh_io.directory_loader(DIR), DIR/<obj_id>.{obj,ply,stl} or the
+                                            single mesh file in DIR/<obj_id>/ (giving both flags is refused)
   --with_gt                                 a second panel beside the refined one: the ground-truth hand (pose decode -> MANO) in a second
                                             colour with the same objects and camera; needs --mano.factory and is refused without it
   --render.contact_map                      every hand panel's vertices are coloured by their distance to the clip's objects
@@ -41,7 +43,7 @@ import numpy as np
 
 from . import _score_common as C
 from . import formats
-from .compute_score_siv import resolve_loader
+from .compute_score_siv import add_mesh_prefix_argument, mesh_loader, resolve_loader, set_mesh_prefix  # noqa: F401
 
 _logger = logging.getLogger("oakink2_tamf_amd.launch.render_samples")
 PROG = "render_samples"
@@ -58,6 +60,7 @@ def parse_args(argv):
     ap = C.make_parser(PROG)
     ap.add_argument("--data.obj_model_loader", dest="data__obj_model_loader", default=None,
                     help="module:function, function(obj_id) -> (verts, faces): draw the objects as meshes")
+    add_mesh_prefix_argument(ap)
     for key, default in RENDER_DEFAULTS.items():
         ap.add_argument("--render." + key, dest="render__" + key, type=int, default=default)
     ap.add_argument("--render.contact_map", dest="display__contact_map", action="store_true", help="colour the hand by its distance to the objects")
@@ -73,6 +76,7 @@ def parse_args(argv):
     a = ap.parse_args(argv)
     cfg = C.build_config(a)
     cfg["data"]["obj_model_loader"] = a.data__obj_model_loader
+    set_mesh_prefix(ap, a, cfg)
     r = {key: getattr(a, "render__" + key) for key in RENDER_DEFAULTS}
     if not (1 <= r["width"] <= 4096 and 1 <= r["height"] <= 4096):
         ap.error("--render.width and --render.height must lie in [1, 4096]")
@@ -167,7 +171,7 @@ def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     cfg = parse_args(sys.argv[1:] if argv is None else argv)
     rt = cfg["runtime"]
-    loader = resolve_loader(cfg["data"]["obj_model_loader"])
+    loader = mesh_loader(cfg)
     pairs = C.load_pairs(cfg, obj_model_loader=loader)
     if rt["max_clips"] is not None:
         pairs = pairs[: rt["max_clips"]]
@@ -175,7 +179,8 @@ def main(argv=None) -> int:
     if rt["dry_run"]:
         print(json.dumps({"n_clips": len(pairs), "pairs": C.pair_listing(pairs), "sample_refine_filepath": cfg["debug"]["sample_refine_filepath"],
                           "obj_model_loader": cfg["data"]["obj_model_loader"], "out_dir": rt["out_dir"], "render": cfg["render"],
-                          "display": cfg["display"], "with_gt": rt["with_gt"]}))
+                          "display": cfg["display"], "with_gt": rt["with_gt"],
+                          **({"obj_mesh_prefix": cfg["data"]["obj_mesh_prefix"]} if cfg["data"].get("obj_mesh_prefix") else {})}))
         return 0
     import torch
 

@@ -119,6 +119,30 @@ def fold_bn(w, b, gamma, beta, running_mean, running_var, ld_out: Optional[int] 
     return wo, bo
 
 
+def fps_indices(points, num: int, start_index: int = 0):
+    """tamf_pointenc_fps without a model (no weights, no cfg): one cloud `points` (N, >= 3), a float32 tensor on a GPU ->
+    `num` indices (int64, on that device), [0] = start_index.  The entry point, distance and tie rule of HipPointEncoder.fps."""
+    import torch
+
+    from ..hip_backend import _stream_ptr, require_gpu
+
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] < 3 or points.dtype != torch.float32:
+        raise ValueError("fps_indices: expected a float32 tensor of shape (N, >= 3)")
+    device = require_gpu(points.device)
+    N, C = int(points.shape[0]), int(points.shape[1])
+    if not 1 <= N <= N_MAX:
+        raise ValueError(f"fps_indices: {N} points, the FPS kernel takes 1..{N_MAX}")
+    if not 1 <= int(num) <= N or not 0 <= int(start_index) < N:
+        raise ValueError(f"fps_indices: cannot sample {num} of {N} points from index {start_index}")
+    lib = _bind()
+    p = points.detach().contiguous()
+    start = torch.full((1,), int(start_index), dtype=torch.int32, device=device)
+    out = torch.empty((1, int(num)), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _check(lib.tamf_pointenc_fps(p.data_ptr(), start.data_ptr(), 1, N, C, int(num), out.data_ptr(), _stream_ptr(device)))
+    return out[0].long()
+
+
 class HipPointEncoder(NativeModel):
     """The point encoder on the GPU.  `cfg`: the fields of DEFAULT_CFG (missing ones take their defaults).  A missing kernel library
     or a device that is no GPU is an error; there is no torch fall-back."""
@@ -284,4 +308,4 @@ class HipPointEncoder(NativeModel):
     __call__ = encode
 
 
-__all__ = ["HipPointEncoder", "PointEncoderError", "DEFAULT_CFG", "PREFIX", "make_cfg", "expected_shapes", "map_checkpoint", "fold_bn"]
+__all__ = ["HipPointEncoder", "PointEncoderError", "DEFAULT_CFG", "PREFIX", "make_cfg", "expected_shapes", "map_checkpoint", "fold_bn", "fps_indices"]
