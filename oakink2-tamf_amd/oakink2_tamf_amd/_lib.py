@@ -17,6 +17,8 @@ that description:
            depth peeling, composite, supersampling resolve)
   SURFACE  csrc/tamf_surface.hip -> libtamf_surface.so (include/tamf_surface.h: the bit-defined surface sampler behind the object point
            clouds - face areas, block scan with a fixed carry pass, Philox draw + binary search on the CDF)
+  MESHDIST csrc/tamf_meshdist.hip -> libtamf_meshdist.so (include/tamf_meshdist.h: the bit-defined point-to-mesh distance behind the
+           penetration depth score and process_sdf - triangle tiles with boxes, culled sweep, the inside test of tamf_mesh_contains)
 POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
 score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
 ENCTRAIN, REFINETRAIN and MDMTRAIN share tamf_train_host.h (the table of bound tensors, the context base, the call checks, the
@@ -49,6 +51,7 @@ MDMTRAIN_LIB_PATH = os.path.join(LIB_DIR, "libtamf_mdmtrain.so")
 OPTIM_LIB_PATH = os.path.join(LIB_DIR, "libtamf_optim.so")
 RENDER_LIB_PATH = os.path.join(LIB_DIR, "libtamf_render.so")
 SURFACE_LIB_PATH = os.path.join(LIB_DIR, "libtamf_surface.so")
+MESHDIST_LIB_PATH = os.path.join(LIB_DIR, "libtamf_meshdist.so")
 
 EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_ctx_create", "tamf_ctx_resize", "tamf_ctx_destroy", "tamf_last_error", "tamf_load_weight", "tamf_finalize_weights",
@@ -102,6 +105,10 @@ RENDER_EXPORTS = [  # include/tamf_render.h: what libtamf_render.so exports
 ]
 SURFACE_EXPORTS = [  # include/tamf_surface.h: what libtamf_surface.so exports
     "tamf_surface_last_error", "tamf_surface_workspace_bytes", "tamf_surface_sample",
+]
+MESHDIST_EXPORTS = [  # include/tamf_meshdist.h: what libtamf_meshdist.so exports
+    "tamf_meshdist_last_error", "tamf_meshdist_workspace", "tamf_meshdist_prepare", "tamf_meshdist_points_workspace", "tamf_meshdist_points",
+    "tamf_meshdist_lattice",
 ]
 
 
@@ -326,6 +333,9 @@ RENDER = Library("libtamf_render", "tamf_render.hip", ("tamf_render.h", "tamf_hi
 SURFACE = Library("libtamf_surface", "tamf_surface.hip", ("tamf_surface.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
                   (Output("libtamf_surface.so", ("-ffp-contract=off",), SURFACE_EXPORTS),),
                   kernels=("_Z24surface_area_scan_kernel", "_Z20surface_carry_kernel", "_Z24surface_add_carry_kernel", "_Z21surface_sample_kernel"))
+MESHDIST = Library("libtamf_meshdist", "tamf_meshdist.hip", ("tamf_meshdist.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
+                   (Output("libtamf_meshdist.so", ("-ffp-contract=off",), MESHDIST_EXPORTS),),
+                   kernels=("_Z24md_inside_prepare_kernel", "_Z22meshdist_points_kernel", "_Z23meshdist_lattice_kernel"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)
@@ -335,11 +345,12 @@ DENOISER_TRAINING = (MDMTRAIN,)  # the denoiser's training step (model/interacti
 OPTIMISER = (OPTIM,)  # the optimiser step of the train / train_refine launchers (optim.py); a group of its own for the same reason
 RENDERING = (RENDER,)  # the offscreen renderer behind launch/render_samples.py (render.py); a group of its own for the same reason
 OBJECT_PREPROCESSING = (SURFACE,)  # the surface sampler behind launch/sample_object_points.py (surface.py); a group of its own for the same reason
+OBJECT_DISTANCE = (MESHDIST,)  # the point-to-mesh distance behind the PD score, process_sdf and the penetration map (meshdist.py); a group of its own for the same reason
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Every library, the sampler pair first, each only when ITS sources changed.  One library at a time.  Returns LIB_PATH."""
-    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING + OPTIMISER + RENDERING + OBJECT_PREPROCESSING:
+    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING + OPTIMISER + RENDERING + OBJECT_PREPROCESSING + OBJECT_DISTANCE:
         lib.build(force, verbose)
     return LIB_PATH
 
@@ -431,6 +442,11 @@ def load_render() -> ctypes.CDLL:
 def load_surface() -> ctypes.CDLL:
     """libtamf_surface.so (include/tamf_surface.h).  Independent of the other libraries."""
     return _load(SURFACE, "libtamf_surface.so")
+
+
+def load_meshdist() -> ctypes.CDLL:
+    """libtamf_meshdist.so (include/tamf_meshdist.h).  Independent of the other libraries."""
+    return _load(MESHDIST, "libtamf_meshdist.so")
 
 
 def load_from(path: str) -> ctypes.CDLL:

@@ -8,7 +8,7 @@ an Open3D window and dev_fn/util/vis_pyrender_util.py renders through OpenGL; a 
         [--data.obj_model_loader pkg.mod:load_obj] [--with_gt --mano.factory pkg.mod:make_mano] [--render.width 512] [--render.height 512]
         [--render.every 1] [--render.sheet_cols 8] [--render.point_size 3] [--max_clips N] [--device cuda:0] [--out_json index.json] [--dry_run]
         [--render.contact_map [--render.contact_far_mm 30]] [--render.obj_alpha 1.0] [--render.layers K] [--render.ssaa 1]
-        [--render.apng [--render.apng_fps 10]]
+        [--render.apng [--render.apng_fps 10]] [--render.penetration_map [--render.penetration_far_mm 10]]
 
 The `--data.*`, `--debug.sample_refine_filepath` and `--mano.*` names of compute_score_cr.py (launch/_score_common.py), and:
   --data.obj_model_loader module:function   function(obj_id) -> (verts, faces), as compute_score_siv.py takes it: the objects are drawn
@@ -21,6 +21,12 @@ The `--data.*`, `--debug.sample_refine_filepath` and `--mano.*` names of compute
                                             (contact.merged_h2o_dist against `obj_pointcloud` moved along `obj_traj`): the contact colour at
                                             5 mm (the CR score's threshold) and nearer, the hand's own colour from --render.contact_far_mm
                                             (a display default) on; refused when the item carries no point cloud.  On the hand only.
+  --render.penetration_map                  every hand panel's vertices that lie INSIDE an object are coloured by how deep they are: the
+                                            hand's own colour at depth 0 to the penetration colour at --render.penetration_far_mm (a
+                                            display default, not a measurement) and deeper; depth = the exact distance to the object's
+                                            mesh (meshdist.py), inside = the test of the SIV and PD scores.  Needs the objects' meshes
+                                            (refused without --data.obj_model_loader / --data.obj_mesh_prefix) and is refused together
+                                            with --render.contact_map.  One MeshSet.distance call per clip.
   --render.obj_alpha A                      the objects are drawn see-through with alpha A in (0, 1]: the fingers behind them show
   --render.layers K                         depth layers peeled per pixel, 1 .. 8 (default 1, and 4 when obj_alpha < 1)
   --render.ssaa S                           S x S sub-samples a pixel, 1 .. 4 (default 1)
@@ -53,6 +59,8 @@ RENDER_DEFAULTS = {"width": 512, "height": 512, "every": 1, "sheet_cols": 8, "po
 CONTACT_COLOR = (1.0, 0.1, 0.05)
 CONTACT_NEAR = 0.005  # metres: the contact threshold of the CR score
 # what draws the picture differently; kept apart from cfg["render"], which stays the five sizes above
+PENETRATION_COLOR = (0.55, 0.10, 0.85)
+PENETRATION_FAR_MM = 10.0  # a display default, not a measurement
 DISPLAY_DEFAULTS = {"contact_map": False, "contact_far_mm": 30.0, "obj_alpha": 1.0, "layers": 1, "ssaa": 1, "apng": False, "apng_fps": 10}
 
 
@@ -70,6 +78,8 @@ def parse_args(argv):
     ap.add_argument("--render.ssaa", dest="display__ssaa", type=int, default=DISPLAY_DEFAULTS["ssaa"])
     ap.add_argument("--render.apng", dest="display__apng", action="store_true", help="also write clip.apng")
     ap.add_argument("--render.apng_fps", dest="display__apng_fps", type=int, default=DISPLAY_DEFAULTS["apng_fps"])
+    ap.add_argument("--render.penetration_map", dest="penetration__map", action="store_true", help="colour the hand vertices inside an object by their depth")
+    ap.add_argument("--render.penetration_far_mm", dest="penetration__far_mm", type=float, default=None)
     ap.add_argument("--out_dir", default=os.path.join("common", "render_samples", "main"))
     ap.add_argument("--max_clips", type=int, default=None, help="render the first N clips only")
     ap.add_argument("--with_gt", action="store_true", help="second panel: the ground-truth hand (needs --mano.factory)")
@@ -103,6 +113,18 @@ def parse_args(argv):
         ap.error("--render.contact_far_mm must exceed the contact threshold of %g mm" % (1e3 * CONTACT_NEAR))
     if not 1 <= d["apng_fps"] <= 1000:
         ap.error("--render.apng_fps must lie in [1, 1000]")
+    if a.penetration__far_mm is not None and not a.penetration__map:
+        ap.error("--render.penetration_far_mm belongs to --render.penetration_map")
+    if a.penetration__map:  # cfg["penetration"]: present only when the flag is given, so a run without it is configured exactly as before
+        if d["contact_map"]:
+            ap.error("--render.penetration_map and --render.contact_map both colour the hand: give one")
+        if a.data__obj_model_loader is None and a.data__obj_mesh_prefix is None:
+            ap.error("--render.penetration_map measures the hand against the objects' meshes: pass --data.obj_model_loader module:function "
+                     "or --data.obj_mesh_prefix DIR")
+        far = PENETRATION_FAR_MM if a.penetration__far_mm is None else a.penetration__far_mm
+        if not (far > 0.0 and np.isfinite(far)):
+            ap.error("--render.penetration_far_mm must be a positive number")
+        cfg["penetration"] = {"far_mm": float(far)}
     cfg["render"] = r
     cfg["display"] = d
     cfg["runtime"].update(out_dir=os.path.abspath(a.out_dir), max_clips=a.max_clips, with_gt=a.with_gt)
@@ -136,10 +158,12 @@ def render_clip(item, hands, faces, cfg, device):
         seen.append((np.einsum("fij,pj->fpi", m[frames][:, :, :3], s) + m[frames][:, None, :, 3]).reshape(-1, 3))
     cam = R.look_at_camera(np.concatenate(seen), r["width"], r["height"])
     panels = []
-    for verts, colour in hands:
+    pen = penetration_maps(item, hands, frames, cfg["penetration"]["far_mm"], device) if "penetration" in cfg else None
+    for n_panel, (verts, colour) in enumerate(hands):
         rd = R.HipRenderer(r["width"], r["height"], device)
         hand = np.asarray(verts, np.float32)[frames]
-        rd.add_mesh(hand, faces, color=colour, smooth=True, name="hand", vertex_colors=contact_map(item, hand, frames, colour, d, device) if d["contact_map"] else None)
+        vcol = contact_map(item, hand, frames, colour, d, device) if d["contact_map"] else pen[n_panel] if pen is not None else None
+        rd.add_mesh(hand, faces, color=colour, smooth=True, name="hand", vertex_colors=vcol)
         for k, (m, s) in enumerate(zip(poses, shapes)):
             colour_k = OBJ_COLORS[k % len(OBJ_COLORS)]
             if meshes:
@@ -167,6 +191,39 @@ def contact_map(item, hand, frames, colour, d, device):
     return R.contact_colors(dist, colour, hot=CONTACT_COLOR, near=CONTACT_NEAR, far=1e-3 * d["contact_far_mm"])
 
 
+def penetration_depths(item, hands, frames, device):
+    """Per panel the depth of every hand vertex at the drawn frames: hands [(verts (T, V, 3), colour)] -> depth (panels, n, V) float64
+    metres and inside (panels, n, V) bool, on the device.  A vertex's depth is its largest distance to the mesh of an object it lies
+    inside (0 outside all of them); poses and their inverses as the PD score takes them (metrics/pd.py).  All frames, panels and
+    objects of the clip go through ONE MeshSet.distance call."""
+    import torch
+
+    from ..meshdist import MeshSet
+    from ..metrics.pd import inverse_transf
+    from ..metrics.siv import tslrot6d_to_transf
+
+    if "obj_verts" not in item:
+        raise SystemExit(f"--render.penetration_map: clip {tuple(item['info'])} carries no object meshes to measure the hand against")
+    nobj, n, P = len(item["obj_list"]), len(frames), len(hands)
+    pts = np.ascontiguousarray(np.stack([np.asarray(v, np.float32)[frames] for v, _ in hands]))  # (P, n, V, 3)
+    V = pts.shape[2]
+    ms = MeshSet([(item["obj_verts"][k], item["obj_faces"][k]) for k in range(nobj)], device=device)
+    inv = inverse_transf(tslrot6d_to_transf(np.asarray(item["obj_traj"])))[:, frames].astype(np.float64)  # (nobj, n, 3, 4)
+    slot = np.arange(P * n, dtype=np.int64).repeat(nobj)  # (panel, frame)-major, the objects innermost
+    obj = np.tile(np.arange(nobj, dtype=np.int64), P * n)
+    dist, _, inside = ms.distance(pts.reshape(-1, 3), obj.astype(np.int32), inv[obj, slot % n], slot * V, np.full(slot.shape, V, np.int64))
+    dist, inside = dist.reshape(P, n, nobj, V), inside.reshape(P, n, nobj, V)
+    return torch.where(inside, dist, torch.zeros_like(dist)).amax(dim=2), inside.any(dim=2)
+
+
+def penetration_maps(item, hands, frames, far_mm, device):
+    """the heat maps of a clip's hand panels: [colours (n, V, 3) float32 on the device, one per panel]"""
+    from .. import render as R
+
+    depth, inside = penetration_depths(item, hands, frames, device)
+    return [R.penetration_colors(depth[p], inside[p], colour, hot=PENETRATION_COLOR, far=1e-3 * far_mm) for p, (_, colour) in enumerate(hands)]
+
+
 def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     cfg = parse_args(sys.argv[1:] if argv is None else argv)
@@ -179,7 +236,7 @@ def main(argv=None) -> int:
     if rt["dry_run"]:
         print(json.dumps({"n_clips": len(pairs), "pairs": C.pair_listing(pairs), "sample_refine_filepath": cfg["debug"]["sample_refine_filepath"],
                           "obj_model_loader": cfg["data"]["obj_model_loader"], "out_dir": rt["out_dir"], "render": cfg["render"],
-                          "display": cfg["display"], "with_gt": rt["with_gt"],
+                          "display": cfg["display"], "with_gt": rt["with_gt"], **({"penetration": cfg["penetration"]} if "penetration" in cfg else {}),
                           **({"obj_mesh_prefix": cfg["data"]["obj_mesh_prefix"]} if cfg["data"].get("obj_mesh_prefix") else {})}))
         return 0
     import torch
@@ -223,6 +280,8 @@ def main(argv=None) -> int:
            "with_gt": rt["with_gt"], "clips": index}
     if cfg["display"] != DISPLAY_DEFAULTS:
         res["display"] = cfg["display"]
+    if "penetration" in cfg:
+        res["penetration"] = cfg["penetration"]
     print(f"n_frames {res['n_frames']}")
     if rt["out_json"]:
         C.write_json(rt["out_json"], res)

@@ -452,6 +452,27 @@ def contact_colors(dist, base, hot=(1.0, 0.1, 0.05), near: float = 0.005, far: f
     return (np.float32(1.0) - w)[..., None] * b + w[..., None] * h
 
 
+def penetration_colors(depth, inside, base, hot=(0.55, 0.10, 0.85), far: float = 0.01):
+    """depths (...) in metres and inside (...) bool (meshdist.MeshSet.distance: distance of a hand vertex to an object's mesh, and
+    whether it lies inside it; tensors stay on their device, anything else goes through numpy) -> colours (..., 3) float32:
+    w = clamp(depth / far, 0, 1) where inside, 0 elsewhere; colour = (1 - w) * base + w * hot: exactly `base` outside and at depth 0,
+    exactly `hot` at depth >= far.  far is a display default, not a measurement."""
+    if not float(far) > 0.0:
+        raise ValueError(f"penetration_colors: far must be positive, got {far}")
+    if hasattr(depth, "detach"):
+        import torch
+
+        d = depth.detach().to(torch.float32)
+        m = torch.as_tensor(inside, device=d.device).to(torch.bool)
+        b, h = (torch.tensor([float(x) for x in c], dtype=torch.float32, device=d.device) for c in (base, hot))
+        w = torch.where(m, (d / float(far)).clamp(0.0, 1.0), torch.zeros_like(d))
+        return (1.0 - w)[..., None] * b + w[..., None] * h
+    d = np.asarray(depth, np.float32)
+    b, h = _floats(base, 3), _floats(hot, 3)
+    w = np.where(np.asarray(inside, bool), np.clip(d / np.float32(far), 0.0, 1.0), 0.0).astype(np.float32)
+    return (np.float32(1.0) - w)[..., None] * b + w[..., None] * h
+
+
 # ---- images ---------------------------------------------------------------------------------------------------------------------
 def _png_chunk(tag: bytes, data: bytes) -> bytes:
     return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
@@ -596,5 +617,5 @@ def contact_sheet(frames, cols: int, background=0) -> np.ndarray:
     return sheet
 
 
-__all__ = ["Camera", "HipRenderer", "look_at_camera", "default_lights", "write_png", "read_png", "write_apng", "read_apng", "contact_colors",
+__all__ = ["Camera", "HipRenderer", "look_at_camera", "default_lights", "write_png", "read_png", "write_apng", "read_apng", "contact_colors", "penetration_colors",
            "contact_sheet", "tslrot6d_to_matrix", "AMBIENT"]
