@@ -19,6 +19,8 @@ that description:
            clouds - face areas, block scan with a fixed carry pass, Philox draw + binary search on the CDF)
   MESHDIST csrc/tamf_meshdist.hip -> libtamf_meshdist.so (include/tamf_meshdist.h: the bit-defined point-to-mesh distance behind the
            penetration depth score and process_sdf - triangle tiles with boxes, culled sweep, the inside test of tamf_mesh_contains)
+  SDFGRID  csrc/tamf_sdfgrid.hip -> libtamf_sdfgrid.so (include/tamf_sdfgrid.h: the bit-defined SDF-lattice sampler behind the training
+           losses' `pen` term - pose transform and trilinear read of the lattices process_sdf writes, forward and backward)
 POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
 score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
 ENCTRAIN, REFINETRAIN and MDMTRAIN share tamf_train_host.h (the table of bound tensors, the context base, the call checks, the
@@ -52,6 +54,7 @@ OPTIM_LIB_PATH = os.path.join(LIB_DIR, "libtamf_optim.so")
 RENDER_LIB_PATH = os.path.join(LIB_DIR, "libtamf_render.so")
 SURFACE_LIB_PATH = os.path.join(LIB_DIR, "libtamf_surface.so")
 MESHDIST_LIB_PATH = os.path.join(LIB_DIR, "libtamf_meshdist.so")
+SDFGRID_LIB_PATH = os.path.join(LIB_DIR, "libtamf_sdfgrid.so")
 
 EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_ctx_create", "tamf_ctx_resize", "tamf_ctx_destroy", "tamf_last_error", "tamf_load_weight", "tamf_finalize_weights",
@@ -109,6 +112,9 @@ SURFACE_EXPORTS = [  # include/tamf_surface.h: what libtamf_surface.so exports
 MESHDIST_EXPORTS = [  # include/tamf_meshdist.h: what libtamf_meshdist.so exports
     "tamf_meshdist_last_error", "tamf_meshdist_workspace", "tamf_meshdist_prepare", "tamf_meshdist_points_workspace", "tamf_meshdist_points",
     "tamf_meshdist_lattice",
+]
+SDFGRID_EXPORTS = [  # include/tamf_sdfgrid.h: what libtamf_sdfgrid.so exports
+    "tamf_sdfgrid_last_error", "tamf_sdfgrid_forward", "tamf_sdfgrid_backward",
 ]
 
 
@@ -336,6 +342,9 @@ SURFACE = Library("libtamf_surface", "tamf_surface.hip", ("tamf_surface.h", "tam
 MESHDIST = Library("libtamf_meshdist", "tamf_meshdist.hip", ("tamf_meshdist.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
                    (Output("libtamf_meshdist.so", ("-ffp-contract=off",), MESHDIST_EXPORTS),),
                    kernels=("_Z24md_inside_prepare_kernel", "_Z22meshdist_points_kernel", "_Z23meshdist_lattice_kernel"))
+SDFGRID = Library("libtamf_sdfgrid", "tamf_sdfgrid.hip", ("tamf_sdfgrid.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
+                  (Output("libtamf_sdfgrid.so", ("-ffp-contract=off",), SDFGRID_EXPORTS),),
+                  kernels=("_Z22sdfgrid_forward_kernel", "_Z23sdfgrid_backward_kernel"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)
@@ -346,11 +355,12 @@ OPTIMISER = (OPTIM,)  # the optimiser step of the train / train_refine launchers
 RENDERING = (RENDER,)  # the offscreen renderer behind launch/render_samples.py (render.py); a group of its own for the same reason
 OBJECT_PREPROCESSING = (SURFACE,)  # the surface sampler behind launch/sample_object_points.py (surface.py); a group of its own for the same reason
 OBJECT_DISTANCE = (MESHDIST,)  # the point-to-mesh distance behind the PD score, process_sdf and the penetration map (meshdist.py); a group of its own for the same reason
+PENETRATION_LOSS = (SDFGRID,)  # the SDF-lattice sampler behind the training losses' `pen` term (sdfgrid.py); a group of its own for the same reason
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Every library, the sampler pair first, each only when ITS sources changed.  One library at a time.  Returns LIB_PATH."""
-    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING + OPTIMISER + RENDERING + OBJECT_PREPROCESSING + OBJECT_DISTANCE:
+    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING + OPTIMISER + RENDERING + OBJECT_PREPROCESSING + OBJECT_DISTANCE + PENETRATION_LOSS:
         lib.build(force, verbose)
     return LIB_PATH
 
@@ -447,6 +457,11 @@ def load_surface() -> ctypes.CDLL:
 def load_meshdist() -> ctypes.CDLL:
     """libtamf_meshdist.so (include/tamf_meshdist.h).  Independent of the other libraries."""
     return _load(MESHDIST, "libtamf_meshdist.so")
+
+
+def load_sdfgrid() -> ctypes.CDLL:
+    """libtamf_sdfgrid.so (include/tamf_sdfgrid.h).  Independent of the other libraries."""
+    return _load(SDFGRID, "libtamf_sdfgrid.so")
 
 
 def load_from(path: str) -> ctypes.CDLL:

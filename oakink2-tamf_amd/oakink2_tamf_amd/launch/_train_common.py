@@ -67,10 +67,11 @@ DEFAULTS = {  # reference launch/train.py:60-271 (paths relative to the working 
     "mano.factory": None,
     "train.optimizer": "hip",
     "train.start_epoch": 0,
+    "data.obj_sdf_prefix": None,
 }
 PATH_KEYS = ("data.data_prefix", "data.obj_embedding_prefix", "data.obj_pointcloud_prefix", "train.cache_dict_filepath", "val.cache_dict_filepath",
              "test.cache_dict_filepath", "train.reload_ckpt_model_filepath", "train.reload_ckpt_optimizer_filepath", "train.loss.vpe_path",
-             "train.loss.c_weight_path", "mano.mano_path", "data.text_embedding_filepath")
+             "train.loss.c_weight_path", "mano.mano_path", "data.text_embedding_filepath", "data.obj_sdf_prefix")
 PATH_LIST_KEYS = ("train.data.pose_repr_sample_dir_list", "val.data.pose_repr_sample_dir_list", "test.data.pose_repr_sample_dir_list")
 CONVERT = {"train.batch_size": int, "val.batch_size": int, "test.batch_size": int, "train.num_epoch": int, "train.record_freq": int,
            "train.scheduler_milestone": _int_list, "train.scheduler_gamma": float, "val.val_freq": int, "test.test_freq": int,
@@ -80,11 +81,15 @@ CONVERT = {"train.batch_size": int, "val.batch_size": int, "test.batch_size": in
            "test.data.pose_repr_sample_dir_list": _path_list, "train.data.gaussian_perturb_range": _float_list}
 
 
-def parse_args(argv: List[str], prog: str, model_defaults: Dict, loss_coefs: Sequence[str], extra_defaults: Dict, exp_default: str) -> Dict:
+def parse_args(argv: List[str], prog: str, model_defaults: Dict, loss_coefs: Sequence[str], extra_defaults: Dict, exp_default: str,
+               own_coefs: Sequence[str] = ()) -> Dict:
     """-> the resolved options: yml presets merged in order, then the command line over them; `loss_coefs` are the launcher's
-    --train.loss.coef_* names (default 0.0, launch/param/loss.py / loss_refine.py), `extra_defaults` its own dotted options"""
-    defaults = {**DEFAULTS, **{f"train.loss.{c}": 0.0 for c in loss_coefs}, **extra_defaults}
-    convert = {**CONVERT, **{f"train.loss.{c}": float for c in loss_coefs}}
+    --train.loss.coef_* names (default 0.0, launch/param/loss.py / loss_refine.py), `extra_defaults` its own dotted options;
+    `own_coefs` are --train.loss.coef_* of this build's own terms: 0.0 when absent like the others, but listed under train.loss only
+    when a preset or the command line gives them, so that a run without them resolves to the options it always had"""
+    own = {f"train.loss.{c}" for c in own_coefs}
+    defaults = {**DEFAULTS, **{f"train.loss.{c}": 0.0 for c in tuple(loss_coefs) + tuple(own_coefs)}, **extra_defaults}
+    convert = {**CONVERT, **{f"train.loss.{c}": float for c in tuple(loss_coefs) + tuple(own_coefs)}}
     ap = argparse.ArgumentParser(prog=f"oakink2_tamf_amd.launch.{prog}", allow_abbrev=False)
     ap.add_argument("--cfg", action="append", default=[], help="yml preset(s), merged in order: arch_mdm_l.yml, loss_param.yml, bs_64.yml, ...")
     for key in defaults:
@@ -105,6 +110,8 @@ def parse_args(argv: List[str], prog: str, model_defaults: Dict, loss_coefs: Seq
             _merge(cfg, yaml.safe_load(f) or {})
     for key, default in defaults.items():
         val = getattr(a, key.replace(".", "__"))
+        if key in own and val is None and _get(cfg, key, None) is None:
+            continue
         val = convert.get(key, str)(val) if val is not None else _get(cfg, key, default)
         if key in PATH_KEYS and val is not None:
             val = _abspath(val)
@@ -171,8 +178,39 @@ def positive_coefs(cfg: Dict) -> Dict[str, float]:
     return {k: float(v) for k, v in cfg["train"]["loss"].items() if k.startswith("coef_") and float(v or 0.0) > 0.0}
 
 
-def load_loss(cfg: Dict, device, coefs: Sequence[str]):
-    """HandInteractionLoss over the MANO layers of --mano.factory (which must be differentiable) with --train.loss.*"""
+PEN_COEF = "coef_pen_loss"  # this build's own term (model/interaction_loss.py): the excess penetration depth from the objects' SDF lattices
+
+
+def pen_on(cfg: Dict) -> bool:
+    return float(cfg["train"]["loss"].get(PEN_COEF) or 0.0) > 0.0
+
+
+def sdf_grid_set(cfg: Dict, base, device=None, upload: bool = True):
+    """The lattices of the `pen` term: one per distinct object id of the train cache `base` that has a pickle under
+    --data.obj_sdf_prefix.  -> (sdfgrid.SdfGridSet or None, the ids without a pickle); (None, []) when the term is off.  upload=False
+    reads and checks the files and touches no GPU."""
+    if not pen_on(cfg):
+        return None, []
+    prefix = cfg["data"].get("obj_sdf_prefix")
+    if not prefix:
+        raise SystemExit("--train.loss.coef_pen_loss > 0 needs the objects' signed distance files: pass --data.obj_sdf_prefix DIR "
+                         "(script/process_object_sdf.sh writes DIR/<obj_id>.pkl)")
+    if not os.path.isdir(prefix):
+        raise SystemExit(f"--data.obj_sdf_prefix {prefix} is no directory (script/process_object_sdf.sh writes DIR/<obj_id>.pkl)")
+    from ..sdfgrid import SdfGridSet
+
+    try:
+        grids, missing = SdfGridSet.from_prefix(prefix, sorted(set(base.interaction_object_list)), device=device, upload=upload)
+    except ValueError as e:
+        raise SystemExit(f"--data.obj_sdf_prefix: {e}")
+    if grids is None:
+        raise SystemExit(f"--data.obj_sdf_prefix {prefix} holds no <obj_id>.pkl of the train cache's objects (script/process_object_sdf.sh writes them)")
+    return grids, missing
+
+
+def load_loss(cfg: Dict, device, coefs: Sequence[str], sdf_grids=None):
+    """HandInteractionLoss over the MANO layers of --mano.factory (which must be differentiable) with --train.loss.*; `sdf_grids`:
+    sdf_grid_set's lattices when coef_pen_loss is positive"""
     from ..model.interaction_loss import HandInteractionLoss
 
     spec = cfg["mano"].get("factory")
@@ -196,6 +234,8 @@ def load_loss(cfg: Dict, device, coefs: Sequence[str]):
     else:
         vpe = np.zeros((0, 2), np.int64)
     kw = {c: float(lc.get(c) or 0.0) for c in coefs}
+    if kw.get(PEN_COEF, 0.0) > 0.0:
+        kw["sdf_grids"] = sdf_grids
     return HandInteractionLoss(layer_rh, layer_lh, vpe, v_weights, **kw).to(device)
 
 
@@ -210,9 +250,10 @@ def pad_points(clouds: Sequence[np.ndarray]):
     return torch.from_numpy(out)
 
 
-def collate(items: List[Dict], device, fields: Sequence[str], want_points: bool) -> Dict:
-    """interaction_segment_collate, then the float fields in `fields` on the device as float32, hand_side, obj_num as a list of ints
-    and, when asked, obj_points (B, nobj, P, 3) from the items' obj_pointcloud"""
+def collate(items: List[Dict], device, fields: Sequence[str], want_points: bool, grid_index=None) -> Dict:
+    """interaction_segment_collate, then the float fields in `fields` on the device as float32, hand_side, obj_num as a list of ints,
+    when asked obj_points (B, nobj, P, 3) from the items' obj_pointcloud and, with `grid_index` ({obj_id: lattice} of the `pen` term's
+    set), sdf_grid_id (B, nobj) int32 from the items' obj_list"""
     import torch
 
     from ..dataset.batching import interaction_segment_collate
@@ -225,6 +266,10 @@ def collate(items: List[Dict], device, fields: Sequence[str], want_points: bool)
         if "obj_pointcloud" not in full:
             raise SystemExit("the distance losses need the objects' point clouds: pass --data.obj_pointcloud_prefix (config/obj_pointcloud.yml)")
         batch["obj_points"] = pad_points(full["obj_pointcloud"]).to(device)
+    if grid_index is not None:
+        from ..sdfgrid import grid_ids
+
+        batch["sdf_grid_id"] = grid_ids(full["obj_list"], grid_index).to(device)
     return batch
 
 
@@ -331,5 +376,5 @@ def main_common(argv, prog: str, parse: Callable, datasets: Callable, build_fact
     return train_loop(cfg, argv, info, prog, dataset, build_factory(cfg, dataset), run_batch, logger)
 
 
-__all__ = ["parse_args", "base_dataset", "lr_at", "plan", "positive_coefs", "load_loss", "pad_points", "collate", "make_optimizer", "optimizer_step",
+__all__ = ["parse_args", "base_dataset", "lr_at", "plan", "positive_coefs", "load_loss", "pen_on", "sdf_grid_set", "PEN_COEF", "pad_points", "collate", "make_optimizer", "optimizer_step",
            "train_loop", "main_common", "_Concat", "BASE_LR", "CLIP_MAX_NORM"]

@@ -8,7 +8,11 @@ reference calls it per clip and per object in Python; `forward` makes one differ
 one forward-only call for the ground truth.  The hand normals come from geometry.vertex_normals outside the graph: they enter the
 distance through a sign only, which has a zero derivative, so the reference's own autograd sends nothing through them either.
 
-Like the other terms, the two are reduced in float64 and summed over the clips."""
+Like the other terms, the two are reduced in float64 and summed over the clips.
+
+`pen` (coef_pen_loss) is this package's own term, not the reference's: how much deeper the predicted hand's vertices lie inside the
+objects than the ground truth's do, the depth read from the objects' signed distance lattices (sdfgrid.penetration_depth: HIP forward
+and backward).  With its coefficient at 0, the default, nothing of it runs and the loss dict has no `pen` key."""
 from __future__ import annotations
 
 import numpy as np
@@ -25,16 +29,39 @@ class HandInteractionLoss(HandReconstructionLoss):
     """HandReconstructionLoss that accepts positive `coef_dist_h_loss` / `coef_dist_o_loss` (the reference's config/loss_param.yml:
     0.1 / 1.0).  `contact_fn(hand_verts, hand_normals, obj_traj, obj_points, obj_num, want_o2h=...)` -> (o2h_signed, h2o, o2h_idx) per
     object defaults to contact.signed_contact_distance, `normals_fn(verts, faces)` to geometry.vertex_normals; the faces are the
-    layers' `th_faces`.  `v_weights` should be given as the reference loads it, float32: its power 1 / 2.5 is taken in that dtype."""
+    layers' `th_faces`.  `v_weights` should be given as the reference loads it, float32: its power 1 / 2.5 is taken in that dtype.
+    A positive `coef_pen_loss` needs `sdf_grids` (an sdfgrid.SdfGridSet on the device) or `pen_fn(hand_verts, obj_traj, grid_id,
+    obj_num) -> depth (B, nobj, T, V)`, which defaults to the set's penetration_depth; the batch then carries `sdf_grid_id` (B, nobj)."""
 
     def __init__(self, layer_rh, layer_lh, vpe, v_weights, coef_rec_joint_loss, coef_rec_vert_loss, coef_edge_len_loss=0.0,
-                 coef_dist_h_loss=0.0, coef_dist_o_loss=0.0, contact_fn=None, normals_fn=None):
+                 coef_dist_h_loss=0.0, coef_dist_o_loss=0.0, contact_fn=None, normals_fn=None, coef_pen_loss=0.0, sdf_grids=None, pen_fn=None):
         super().__init__(layer_rh, layer_lh, vpe, v_weights, coef_rec_joint_loss, coef_rec_vert_loss, coef_edge_len_loss)
         if coef_dist_h_loss < 0.0 or coef_dist_o_loss < 0.0:
             raise ValueError("coef_dist_h_loss and coef_dist_o_loss must not be negative")
         self.coef_dist_h_loss, self.coef_dist_o_loss = float(coef_dist_h_loss), float(coef_dist_o_loss)
         self.register_buffer("v_weights2", torch.pow(self.v_weights, 1.0 / 2.5))
         self._contact_fn, self._normals_fn = contact_fn, normals_fn
+        if coef_pen_loss < 0.0:
+            raise ValueError("coef_pen_loss must not be negative")
+        if coef_pen_loss > 0.0 and sdf_grids is None and pen_fn is None:
+            raise ValueError("coef_pen_loss > 0 needs the objects' signed distance lattices: pass sdf_grids (sdfgrid.SdfGridSet) or a pen_fn")
+        self.coef_pen_loss = float(coef_pen_loss)
+        self._pen_fn = pen_fn if pen_fn is not None or sdf_grids is None else sdf_grids.penetration_depth
+
+    def _pen_term(self, verts_p, verts_g, mask, obj_traj, grid_id, obj_num):
+        """per-clip `pen`, (nb,) float64: e = relu(depth(prediction) - depth(ground truth)), the excess over what the ground truth
+        itself penetrates (mocap data does, a little), reduced as `dist_h` is in _dist_terms but without vertex weights: masked frames,
+        _mask_coef, the mean over frames and vertices, the mean over the clip's real objects."""
+        f64 = torch.float64
+        with torch.no_grad():
+            depth_g = self._pen_fn(verts_g, obj_traj, grid_id, obj_num)  # (forward only)
+        depth_p = self._pen_fn(verts_p, obj_traj, grid_id, obj_num)
+        nobj = depth_p.shape[1]
+        num = torch.as_tensor([int(n) for n in obj_num], device=depth_p.device)
+        real = (torch.arange(nobj, device=depth_p.device)[None, :] < num[:, None]).to(f64)  # (nb, nobj)
+        coef = self._mask_coef(mask).to(f64) / num.to(f64)
+        e = torch.relu(depth_p - depth_g).to(f64) * mask.to(f64)[:, None, :, None]
+        return coef * (e.mean(dim=(-2, -1)) * real).sum(dim=1)
 
     def _fns(self):
         contact_fn, normals_fn = self._contact_fn, self._normals_fn
@@ -77,17 +104,26 @@ class HandInteractionLoss(HandReconstructionLoss):
     def forward(self, model_output, batch):
         """HandReconstructionLoss.forward's inputs plus batch `obj_traj` (B, nobj, T, 9) = tsl | rot6d, `obj_points` (B, nobj, P, 3) in
         the object frame and `obj_num` (B counts in [1, nobj]; None: all nobj are real).  -> (loss, loss_dict) with the reference's
-        keys; every term is summed over the clips and is a float64 scalar."""
+        keys; every term is summed over the clips and is a float64 scalar.  With a positive coef_pen_loss the batch also carries
+        `sdf_grid_id` (B, nobj) integers (-1: no lattice), the loss gains coef_pen_loss * pen and the dict the key `pen`."""
         dist = self.coef_dist_h_loss > 0.0 or self.coef_dist_o_loss > 0.0
+        pen = self.coef_pen_loss > 0.0
         total = {"rec_joint": 0.0, "rec_vert": 0.0, "edge_len": 0.0, "dist_h": 0.0, "dist_o": 0.0}
+        B = model_output.shape[0]
         if dist:
             obj_traj, obj_points = batch["obj_traj"], batch["obj_points"]
-            B = model_output.shape[0]
             if obj_traj.dim() != 4 or obj_points.dim() != 4 or obj_traj.shape[0] != B or obj_points.shape[0] != B:
                 raise ValueError(f"obj_traj / obj_points: expected (B, nobj, T, 9) and (B, nobj, P, 3) with B = {B}, got "
                                  f"{tuple(obj_traj.shape)} and {tuple(obj_points.shape)}")
+        if pen:
+            total["pen"] = 0.0
+            obj_traj, grid_id = batch["obj_traj"], torch.as_tensor(batch["sdf_grid_id"])
+            if obj_traj.dim() != 4 or obj_traj.shape[0] != B or tuple(grid_id.shape) != (B, obj_traj.shape[1]):
+                raise ValueError(f"obj_traj / sdf_grid_id: expected (B, nobj, T, 9) and (B, nobj) with B = {B}, got "
+                                 f"{tuple(obj_traj.shape)} and {tuple(grid_id.shape)}")
+        if dist or pen:
             obj_num = batch.get("obj_num")
-            obj_num = [int(obj_points.shape[1])] * B if obj_num is None else [int(n) for n in obj_num]
+            obj_num = [int(obj_points.shape[1] if dist else obj_traj.shape[1])] * B if obj_num is None else [int(n) for n in obj_num]
             if len(obj_num) != B:
                 raise ValueError(f"obj_num: expected {B} counts, got {len(obj_num)}")
         for layer, idx, verts_p, joints_p, verts_g, joints_g, mask in self._per_side(model_output, batch):
@@ -96,17 +132,23 @@ class HandInteractionLoss(HandReconstructionLoss):
                 dev = verts_p.device
                 terms["dist_h"], terms["dist_o"] = self._dist_terms(layer, verts_p, verts_g, mask, obj_traj.to(dev)[idx], obj_points.to(dev)[idx],
                                                                     [obj_num[int(i)] for i in idx])
+            if pen:
+                dev = verts_p.device
+                terms["pen"] = self._pen_term(verts_p, verts_g, mask, obj_traj.to(dev)[idx], grid_id.to(dev)[idx], [obj_num[int(i)] for i in idx])
             for key, term in terms.items():
                 if torch.is_tensor(term):
                     total[key] = total[key] + term.sum()
         loss = (self.coef_rec_joint_loss * total["rec_joint"] + self.coef_rec_vert_loss * total["rec_vert"]
                 + self.coef_edge_len_loss * total["edge_len"] + self.coef_dist_h_loss * total["dist_h"] + self.coef_dist_o_loss * total["dist_o"])
+        if pen:
+            loss = loss + self.coef_pen_loss * total["pen"]
         return loss, {"loss": loss, **total}
 
     def refine_terms(self, output, batch):
         """HandReconstructionLoss.refine_terms plus SegmentRefineModelLoss's `dist_h` on output `refine_h2o_dist` / `target_h2o_dist`
-        (B, T, V), the merged hand-to-object distances (contact.merged_h2o_dist carries the gradient).  Every term is the mean over
-        the clips."""
+        (B, T, V), the merged hand-to-object distances (contact.merged_h2o_dist carries the gradient), and, with a positive
+        coef_pen_loss, `pen` on output `refine_hand_verts` / `target_hand_verts` with batch `obj_traj`, `sdf_grid_id` and `obj_num`.
+        Every term is the mean over the clips."""
         loss, d = super().refine_terms(output, batch)
         if self.coef_dist_h_loss > 0.0:
             f64 = torch.float64
@@ -116,6 +158,14 @@ class HandInteractionLoss(HandReconstructionLoss):
             dist_h = (self._mask_coef(mask).to(f64) * e.mean(dim=(-2, -1))).mean()
             loss = loss + self.coef_dist_h_loss * dist_h
             d = {**d, "loss": loss, "dist_h": dist_h}
+        if self.coef_pen_loss > 0.0:
+            r = output["refine_hand_verts"]
+            traj, grid_id = batch["obj_traj"], torch.as_tensor(batch["sdf_grid_id"])
+            obj_num = batch.get("obj_num")
+            obj_num = [int(traj.shape[1])] * r.shape[0] if obj_num is None else [int(n) for n in obj_num]
+            pen = self._pen_term(r, output["target_hand_verts"], batch["mask"].to(r.dtype), traj.to(r.device), grid_id.to(r.device), obj_num).mean()
+            loss = loss + self.coef_pen_loss * pen
+            d = {**d, "loss": loss, "pen": pen}
         return loss, d
 
 

@@ -231,7 +231,7 @@ class InterationSegmentMDMTrainStep(TrainStep):
         """The reference's step launch/train.py:518-529: x_start from batch["pose_repr"] (B, T, input_dim) as (B, input_dim, 1, T),
         training_losses with this step's forward as the model and `loss` (a HandInteractionLoss, or None) as the callback,
         (terms["loss"] * weights).mean() + the extra loss, .backward().  t / weights default to uniform_timesteps, noise to randn.
-        batch as forward() plus "pose_repr" and "mask" (B, T), and what `loss` reads ("obj_points", "obj_num").  Afterwards every
+        batch as forward() plus "pose_repr" and "mask" (B, T), and what `loss` reads ("obj_points", "obj_num", "sdf_grid_id").  Afterwards every
         p.grad holds the gradient of the reference's loss.  -> the loss dict: the terms, "diffusion_loss", "loss" (the total) and,
         with a callback, "extra" (its dict)."""
         dev = self.device
