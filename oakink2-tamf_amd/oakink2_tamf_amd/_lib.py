@@ -21,6 +21,8 @@ that description:
            penetration depth score and process_sdf - triangle tiles with boxes, culled sweep, the inside test of tamf_mesh_contains)
   SDFGRID  csrc/tamf_sdfgrid.hip -> libtamf_sdfgrid.so (include/tamf_sdfgrid.h: the bit-defined SDF-lattice sampler behind the training
            losses' `pen` term - pose transform and trilinear read of the lattices process_sdf writes, forward and backward)
+  WINDING  csrc/tamf_winding.hip -> libtamf_winding.so (include/tamf_winding.h: the generalized winding number behind the `winding` sign of
+           process_sdf, the PD and SIV scores and the penetration map - solid angles summed in a fixed tree, points and lattices)
 POINTENC and TEXTENC share two headers of csrc/, compiled into each: tamf_f32_tower.h (the fp32 GEMM, LayerNorm row and attention
 score tile of the two towers) and tamf_weights.h (the host side: error string, weight table, packer, upload, workspace helpers).
 ENCTRAIN, REFINETRAIN and MDMTRAIN share tamf_train_host.h (the table of bound tensors, the context base, the call checks, the
@@ -55,6 +57,7 @@ RENDER_LIB_PATH = os.path.join(LIB_DIR, "libtamf_render.so")
 SURFACE_LIB_PATH = os.path.join(LIB_DIR, "libtamf_surface.so")
 MESHDIST_LIB_PATH = os.path.join(LIB_DIR, "libtamf_meshdist.so")
 SDFGRID_LIB_PATH = os.path.join(LIB_DIR, "libtamf_sdfgrid.so")
+WINDING_LIB_PATH = os.path.join(LIB_DIR, "libtamf_winding.so")
 
 EXPORTS = [  # include/tamf_hip.h: what libtamf_hip.so exports, nothing else
     "tamf_ctx_create", "tamf_ctx_resize", "tamf_ctx_destroy", "tamf_last_error", "tamf_load_weight", "tamf_finalize_weights",
@@ -115,6 +118,10 @@ MESHDIST_EXPORTS = [  # include/tamf_meshdist.h: what libtamf_meshdist.so export
 ]
 SDFGRID_EXPORTS = [  # include/tamf_sdfgrid.h: what libtamf_sdfgrid.so exports
     "tamf_sdfgrid_last_error", "tamf_sdfgrid_forward", "tamf_sdfgrid_backward",
+]
+WINDING_EXPORTS = [  # include/tamf_winding.h: what libtamf_winding.so exports
+    "tamf_winding_last_error", "tamf_winding_workspace", "tamf_winding_prepare", "tamf_winding_points_workspace", "tamf_winding_points",
+    "tamf_winding_lattice",
 ]
 
 
@@ -345,6 +352,9 @@ MESHDIST = Library("libtamf_meshdist", "tamf_meshdist.hip", ("tamf_meshdist.h", 
 SDFGRID = Library("libtamf_sdfgrid", "tamf_sdfgrid.hip", ("tamf_sdfgrid.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
                   (Output("libtamf_sdfgrid.so", ("-ffp-contract=off",), SDFGRID_EXPORTS),),
                   kernels=("_Z22sdfgrid_forward_kernel", "_Z23sdfgrid_backward_kernel"))
+WINDING = Library("libtamf_winding", "tamf_winding.hip", ("tamf_winding.h", "tamf_hip.h"),  # (tamf_hip.h for the tamf_status enum)
+                  (Output("libtamf_winding.so", ("-ffp-contract=off",), WINDING_EXPORTS),),
+                  kernels=("_Z21winding_points_kernelILb0EE", "_Z21winding_points_kernelILb1EE", "_Z21winding_reduce_kernel", "_Z22winding_lattice_kernel"))
 LIBRARIES = (SAMPLER, EVAL, MANO)  # the sampling and evaluation path
 PREPROCESSING = (POINTENC,)  # what prepares a run's inputs (launch/embed_objects.py); described, built and loaded the same way
 TEXT_PREPROCESSING = (TEXTENC,)  # the same for the prompts (launch/embed_text.py)
@@ -356,11 +366,12 @@ RENDERING = (RENDER,)  # the offscreen renderer behind launch/render_samples.py 
 OBJECT_PREPROCESSING = (SURFACE,)  # the surface sampler behind launch/sample_object_points.py (surface.py); a group of its own for the same reason
 OBJECT_DISTANCE = (MESHDIST,)  # the point-to-mesh distance behind the PD score, process_sdf and the penetration map (meshdist.py); a group of its own for the same reason
 PENETRATION_LOSS = (SDFGRID,)  # the SDF-lattice sampler behind the training losses' `pen` term (sdfgrid.py); a group of its own for the same reason
+OBJECT_SIGN = (WINDING,)  # the winding-number inside test for open and scanned object meshes (winding.py); a group of its own for the same reason
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Every library, the sampler pair first, each only when ITS sources changed.  One library at a time.  Returns LIB_PATH."""
-    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING + OPTIMISER + RENDERING + OBJECT_PREPROCESSING + OBJECT_DISTANCE + PENETRATION_LOSS:
+    for lib in LIBRARIES + PREPROCESSING + TEXT_PREPROCESSING + TRAINING + REFINE_TRAINING + DENOISER_TRAINING + OPTIMISER + RENDERING + OBJECT_PREPROCESSING + OBJECT_DISTANCE + PENETRATION_LOSS + OBJECT_SIGN:
         lib.build(force, verbose)
     return LIB_PATH
 
@@ -462,6 +473,11 @@ def load_meshdist() -> ctypes.CDLL:
 def load_sdfgrid() -> ctypes.CDLL:
     """libtamf_sdfgrid.so (include/tamf_sdfgrid.h).  Independent of the other libraries."""
     return _load(SDFGRID, "libtamf_sdfgrid.so")
+
+
+def load_winding() -> ctypes.CDLL:
+    """libtamf_winding.so (include/tamf_winding.h).  Independent of the other libraries."""
+    return _load(WINDING, "libtamf_winding.so")
 
 
 def load_from(path: str) -> ctypes.CDLL:

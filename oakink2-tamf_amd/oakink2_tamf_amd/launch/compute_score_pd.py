@@ -5,7 +5,7 @@ The reference has no such script; the definition is metrics/pd.py's.
         --data.cache_dict_filepath common/save_cache_dict/main/cache/test.pkl \
         --debug.sample_refine_filepath common/sample_refine/main/sample/test/arch_mdm_l__0399 --mano.factory pkg.mod:make_mano \
         --data.obj_model_loader pkg.mod:load_obj [--stride 20] [--batch_size 64] [--device cuda:0] [--out_json pd.json] [--save_dir DIR]
-        [--dry_run]   (or --data.obj_mesh_prefix DIR in place of --data.obj_model_loader)
+        [--sign parity|winding] [--dry_run]   (or --data.obj_mesh_prefix DIR in place of --data.obj_model_loader)
 
 The argument names of compute_score_siv.py, and `--stride` (every stride-th frame of the first `len` frames of a clip is scored: 20, the
 frames SIV scores).  Clips and hands as in compute_score_cr.py.  Every hand vertex of a scored frame, ground truth and refined, is taken
@@ -16,7 +16,10 @@ per clip.  Printed and written with --out_json:
     gt_pd, refined_pd                                        mean depth over the frames, cm
     gt_pd_max, refined_pd_max                                the deepest frame, cm
     gt_pen_frame_ratio, refined_pen_frame_ratio              the share of frames with any vertex inside an object
-    n_objects_open (with --data.obj_mesh_prefix)             objects whose mesh is not closed: the inside test presumes a closed mesh
+    n_objects_open (with --data.obj_mesh_prefix)             objects whose mesh is not closed: the default inside test presumes a closed mesh
+    sign                                                     the inside test used
+`--sign winding` takes `inside` from the generalized winding number (|w| > 0.5, include/tamf_winding.h) on the same vertices and
+transforms: it needs no closed mesh and equals the default on a clean closed one.  The distance is the same either way.
 `--save_dir DIR` writes the per-frame depths gt.npy / refined.npy there."""
 from __future__ import annotations
 
@@ -43,6 +46,9 @@ def parse_args(argv):
     add_mesh_prefix_argument(ap)
     ap.add_argument("--stride", type=int, default=20, help="every stride-th frame is scored (20: the frames SIV scores)")
     ap.add_argument("--save_dir", default=None, help="write gt.npy / refined.npy here")
+    ap.add_argument("--sign", choices=("parity", "winding"), default=None,
+                    help="which vertices count as inside an object: the reference's ray parity (the default; presumes a closed mesh) or the generalized "
+                         "winding number")
     a = ap.parse_args(argv)
     if a.stride < 1:
         ap.error("--stride must be at least 1")
@@ -53,6 +59,8 @@ def parse_args(argv):
         ap.error(NO_MESH_SOURCE)
     cfg["runtime"]["save_dir"] = a.save_dir
     cfg["runtime"]["stride"] = a.stride
+    if a.sign is not None:  # (present only when the flag is given, so a run without it is configured exactly as before)
+        cfg["runtime"]["sign"] = a.sign
     return cfg
 
 
@@ -60,13 +68,14 @@ def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     cfg = parse_args(sys.argv[1:] if argv is None else argv)
     rt = cfg["runtime"]
+    sign = rt.get("sign", "parity")
     loader = mesh_loader(cfg)
     mesh_prefix = cfg["data"].get("obj_mesh_prefix")
     pairs = C.load_pairs(cfg, obj_model_loader=loader)
     _logger.info("clips with a refined sample: %d", len(pairs))
     if rt["dry_run"]:
         print(json.dumps({"n_clips": len(pairs), "pairs": C.pair_listing(pairs), "sample_refine_filepath": cfg["debug"]["sample_refine_filepath"],
-                          "obj_model_loader": cfg["data"]["obj_model_loader"], "stride": rt["stride"],
+                          "obj_model_loader": cfg["data"]["obj_model_loader"], "stride": rt["stride"], "sign": sign,
                           **({"obj_mesh_prefix": mesh_prefix} if mesh_prefix else {})}))
         return 0
     import torch
@@ -106,13 +115,20 @@ def main(argv=None) -> int:
                 if not rep["closed"]:
                     open_objects.append(obj_id)
                     _logger.info("object %s: the mesh is not closed (%d boundary edges, %d non-manifold edges): which vertices count as inside "
-                                 "rests on a test that presumes a closed mesh", obj_id, rep["n_boundary_edges"], rep["n_nonmanifold_edges"])
+                                 + ("is decided by the winding number (|w| > 0.5)" if sign == "winding" else "rests on a test that presumes a closed mesh"),
+                                 obj_id, rep["n_boundary_edges"], rep["n_nonmanifold_edges"])
     mesh_set = MeshSet(meshes, device=device) if meshes else None
+    winding_set = None
+    if sign == "winding" and meshes:
+        from ..winding import WindingSet
+
+        winding_set = WindingSet(meshes, device=device)  # (MeshSet accepted every mesh: the same validity predicate)
     gt_pd, refined_pd, gt_pen, refined_pen = [], [], [], []
     for (item, path), gt_hv in zip(pairs, gt_verts):
         refined_hv = np.asarray(formats.read_refine_sample(path)["verts"], dtype=np.float32)
         ids = [mesh_of[o] for o in item["obj_list"]] if mesh_set is not None else [None] * len(item["obj_list"])
-        depth, pen = clip_pd(gt_hv, refined_hv, item["obj_traj"], mesh_set, ids, int(item["len"]), stride=rt["stride"])
+        depth, pen = clip_pd(gt_hv, refined_hv, item["obj_traj"], mesh_set, ids, int(item["len"]), stride=rt["stride"], sign=sign,
+                             winding_set=winding_set)
         gt_pd.extend(depth[0].tolist())
         refined_pd.extend(depth[1].tolist())
         gt_pen.extend(pen[0].tolist())
@@ -120,7 +136,7 @@ def main(argv=None) -> int:
     if not gt_pd:
         raise SystemExit("no frame to score: every clip with a refined sample has len 0")
     res = {"n_clips": len(pairs), "n_frames": len(gt_pd), "n_objects": len(mesh_of), "n_objects_skipped": len(skipped), "objects_skipped": skipped,
-           "stride": rt["stride"], **summary(gt_pd, refined_pd, gt_pen, refined_pen)}
+           "stride": rt["stride"], "sign": sign, **summary(gt_pd, refined_pd, gt_pen, refined_pen)}
     if mesh_prefix:
         res.update(n_objects_open=len(open_objects), objects_open=open_objects)
     for key in ("n_clips", "n_frames", "n_objects", "n_objects_skipped"):
@@ -129,6 +145,7 @@ def main(argv=None) -> int:
         print(f"{key} {res[key]!r}")
     if mesh_prefix:
         print(f"n_objects_open {res['n_objects_open']}")
+    print(f"sign {res['sign']}")
     if rt["save_dir"]:
         os.makedirs(rt["save_dir"], exist_ok=True)
         np.save(os.path.join(rt["save_dir"], "gt.npy"), gt_pd)

@@ -47,8 +47,13 @@ def parse_args(argv):
     add_mesh_prefix_argument(ap)
     ap.add_argument("--data.obj_sdf_prefix", dest="data__obj_sdf_prefix", default=None, help="DIR/<obj_id>.pkl overrides the native lattice")
     ap.add_argument("--save_dir", default=None, help="write gt.npy / refined.npy here")
+    ap.add_argument("--data.obj_sign", dest="data__obj_sign", choices=("parity", "winding"), default=None,
+                    help="the inside test of the OBJECTS' voxel sets: the reference's ray parity (the default; presumes a closed mesh) or the generalized "
+                         "winding number; the hand's containment test is the reference's either way")
     a = ap.parse_args(argv)
     cfg = C.build_config(a)
+    if a.data__obj_sign is not None:  # (present only when the flag is given, so a run without it is configured exactly as before)
+        cfg["data"]["obj_sign"] = a.data__obj_sign
     cfg["data"]["obj_model_loader"] = a.data__obj_model_loader
     set_mesh_prefix(ap, a, cfg)
     cfg["data"]["obj_sdf_prefix"] = os.path.abspath(a.data__obj_sdf_prefix) if a.data__obj_sdf_prefix else None
@@ -117,7 +122,7 @@ def main(argv=None) -> int:
         print(json.dumps({"n_clips": len(pairs), "pairs": C.pair_listing(pairs),
                           "sample_refine_filepath": cfg["debug"]["sample_refine_filepath"],
                           "obj_model_loader": cfg["data"]["obj_model_loader"], "obj_sdf_prefix": cfg["data"]["obj_sdf_prefix"],
-                          **({"obj_mesh_prefix": mesh_prefix} if mesh_prefix else {})}))
+                          "obj_sign": cfg["data"].get("obj_sign", "parity"), **({"obj_mesh_prefix": mesh_prefix} if mesh_prefix else {})}))
         return 0
     import torch
 
@@ -132,6 +137,9 @@ def main(argv=None) -> int:
                          "per object id (or --data.obj_mesh_prefix DIR of mesh files), or a pickle per object under --data.obj_sdf_prefix")
     torch.cuda.set_device(device)
     from ..metrics.siv import clip_siv, load_sdf_pickle, object_lattice
+    from ..winding import WindingError
+
+    obj_sign = cfg["data"].get("obj_sign", "parity")
 
     faces_closed = {"rh": np.asarray(mano[2]), "lh": np.asarray(mano[3])}
     _, gt_verts = C.ground_truth_mano(items, mano, device, rt["batch_size"])
@@ -149,10 +157,10 @@ def main(argv=None) -> int:
                 if pkl is not None:
                     lattice_map[obj_id] = load_sdf_pickle(pkl)
                 elif "obj_verts" in item:
-                    lattice_map[obj_id] = object_lattice(item["obj_verts"][k], item["obj_faces"][k], device=device)
+                    lattice_map[obj_id] = object_lattice(item["obj_verts"][k], item["obj_faces"][k], device=device, sign=obj_sign)
                 else:
                     lattice_map[obj_id] = None
-            except (ValueError, IndexError, AssertionError, KeyError, pickle.UnpicklingError) as e:
+            except (ValueError, IndexError, AssertionError, KeyError, pickle.UnpicklingError, WindingError) as e:
                 # what a bad mesh or pickle raises in the host half (wrong shapes, face indices outside the vertices, no faces, missing
                 # fields): the object is left out.  Library, build and HIP errors (TamfError, TamfBuildError) are not caught.
                 _logger.info("object %s: no lattice (%s)", obj_id, e)
@@ -165,8 +173,9 @@ def main(argv=None) -> int:
                 rep = mesh_report(item["obj_verts"][k], item["obj_faces"][k])
                 if not rep["closed"]:
                     open_objects.append(obj_id)
-                    _logger.info("object %s: the mesh is not closed (%d boundary edges, %d non-manifold edges): its SIV rests on an inside "
-                                 "test that presumes a closed mesh", obj_id, rep["n_boundary_edges"], rep["n_nonmanifold_edges"])
+                    _logger.info("object %s: the mesh is not closed (%d boundary edges, %d non-manifold edges): its SIV rests on "
+                                 + ("the winding number's inside test (|w| > 0.5)" if obj_sign == "winding" else "an inside test that presumes a closed mesh"),
+                                 obj_id, rep["n_boundary_edges"], rep["n_nonmanifold_edges"])
         g, r = clip_siv(gt_hv, refined_hv, faces_closed[item["hand_side"]], item["obj_traj"], [lattice_map[o] for o in item["obj_list"]],
                         int(item["len"]), device=device)
         gt_siv.extend(g)
@@ -174,13 +183,14 @@ def main(argv=None) -> int:
     if not gt_siv:
         raise SystemExit("no frame to score: every clip with a refined sample has len 0")
     res = {"n_clips": len(pairs), "n_frames": len(gt_siv), "n_objects": len(lattice_map), "n_objects_skipped": len(skipped),
-           "objects_skipped": skipped, "gt_siv": float(np.mean(gt_siv)), "refined_siv": float(np.mean(refined_siv))}
+           "objects_skipped": skipped, "gt_siv": float(np.mean(gt_siv)), "refined_siv": float(np.mean(refined_siv)), "obj_sign": obj_sign}
     if mesh_prefix:
         res.update(n_objects_open=len(open_objects), objects_open=open_objects)
     print(f"n_frames {res['n_frames']}")
     print(f"n_objects_skipped {res['n_objects_skipped']}")
     print(f"gt_siv {res['gt_siv']!r}")
     print(f"refined_siv {res['refined_siv']!r}")
+    print(f"obj_sign {res['obj_sign']}")
     if rt["save_dir"]:
         os.makedirs(rt["save_dir"], exist_ok=True)
         np.save(os.path.join(rt["save_dir"], "gt.npy"), gt_siv)

@@ -8,7 +8,7 @@ an Open3D window and dev_fn/util/vis_pyrender_util.py renders through OpenGL; a 
         [--data.obj_model_loader pkg.mod:load_obj] [--with_gt --mano.factory pkg.mod:make_mano] [--render.width 512] [--render.height 512]
         [--render.every 1] [--render.sheet_cols 8] [--render.point_size 3] [--max_clips N] [--device cuda:0] [--out_json index.json] [--dry_run]
         [--render.contact_map [--render.contact_far_mm 30]] [--render.obj_alpha 1.0] [--render.layers K] [--render.ssaa 1]
-        [--render.apng [--render.apng_fps 10]] [--render.penetration_map [--render.penetration_far_mm 10]]
+        [--render.apng [--render.apng_fps 10]] [--render.penetration_map [--render.penetration_far_mm 10] [--render.penetration_sign parity|winding]]
 
 The `--data.*`, `--debug.sample_refine_filepath` and `--mano.*` names of compute_score_cr.py (launch/_score_common.py), and:
   --data.obj_model_loader module:function   function(obj_id) -> (verts, faces), as compute_score_siv.py takes it: the objects are drawn
@@ -80,6 +80,9 @@ def parse_args(argv):
     ap.add_argument("--render.apng_fps", dest="display__apng_fps", type=int, default=DISPLAY_DEFAULTS["apng_fps"])
     ap.add_argument("--render.penetration_map", dest="penetration__map", action="store_true", help="colour the hand vertices inside an object by their depth")
     ap.add_argument("--render.penetration_far_mm", dest="penetration__far_mm", type=float, default=None)
+    ap.add_argument("--render.penetration_sign", dest="penetration__sign", choices=("parity", "winding"), default=None,
+                    help="which vertices count as inside an object: the reference's ray parity (the default; presumes a closed mesh) or the "
+                         "generalized winding number")
     ap.add_argument("--out_dir", default=os.path.join("common", "render_samples", "main"))
     ap.add_argument("--max_clips", type=int, default=None, help="render the first N clips only")
     ap.add_argument("--with_gt", action="store_true", help="second panel: the ground-truth hand (needs --mano.factory)")
@@ -115,6 +118,8 @@ def parse_args(argv):
         ap.error("--render.apng_fps must lie in [1, 1000]")
     if a.penetration__far_mm is not None and not a.penetration__map:
         ap.error("--render.penetration_far_mm belongs to --render.penetration_map")
+    if a.penetration__sign is not None and not a.penetration__map:
+        ap.error("--render.penetration_sign belongs to --render.penetration_map")
     if a.penetration__map:  # cfg["penetration"]: present only when the flag is given, so a run without it is configured exactly as before
         if d["contact_map"]:
             ap.error("--render.penetration_map and --render.contact_map both colour the hand: give one")
@@ -125,6 +130,8 @@ def parse_args(argv):
         if not (far > 0.0 and np.isfinite(far)):
             ap.error("--render.penetration_far_mm must be a positive number")
         cfg["penetration"] = {"far_mm": float(far)}
+        if a.penetration__sign is not None:  # (present only when given: a run without the flag is configured, and reported, exactly as before)
+            cfg["penetration"]["sign"] = a.penetration__sign
     cfg["render"] = r
     cfg["display"] = d
     cfg["runtime"].update(out_dir=os.path.abspath(a.out_dir), max_clips=a.max_clips, with_gt=a.with_gt)
@@ -158,7 +165,7 @@ def render_clip(item, hands, faces, cfg, device):
         seen.append((np.einsum("fij,pj->fpi", m[frames][:, :, :3], s) + m[frames][:, None, :, 3]).reshape(-1, 3))
     cam = R.look_at_camera(np.concatenate(seen), r["width"], r["height"])
     panels = []
-    pen = penetration_maps(item, hands, frames, cfg["penetration"]["far_mm"], device) if "penetration" in cfg else None
+    pen = penetration_maps(item, hands, frames, cfg["penetration"]["far_mm"], device, cfg["penetration"].get("sign", "parity")) if "penetration" in cfg else None
     for n_panel, (verts, colour) in enumerate(hands):
         rd = R.HipRenderer(r["width"], r["height"], device)
         hand = np.asarray(verts, np.float32)[frames]
@@ -191,11 +198,12 @@ def contact_map(item, hand, frames, colour, d, device):
     return R.contact_colors(dist, colour, hot=CONTACT_COLOR, near=CONTACT_NEAR, far=1e-3 * d["contact_far_mm"])
 
 
-def penetration_depths(item, hands, frames, device):
+def penetration_depths(item, hands, frames, device, sign="parity"):
     """Per panel the depth of every hand vertex at the drawn frames: hands [(verts (T, V, 3), colour)] -> depth (panels, n, V) float64
     metres and inside (panels, n, V) bool, on the device.  A vertex's depth is its largest distance to the mesh of an object it lies
     inside (0 outside all of them); poses and their inverses as the PD score takes them (metrics/pd.py).  All frames, panels and
-    objects of the clip go through ONE MeshSet.distance call."""
+    objects of the clip go through ONE MeshSet.distance call; with sign="winding" `inside` comes from one WindingSet.points call on
+    the same jobs (the generalized winding number, for object meshes that are not closed)."""
     import torch
 
     from ..meshdist import MeshSet
@@ -211,16 +219,22 @@ def penetration_depths(item, hands, frames, device):
     inv = inverse_transf(tslrot6d_to_transf(np.asarray(item["obj_traj"])))[:, frames].astype(np.float64)  # (nobj, n, 3, 4)
     slot = np.arange(P * n, dtype=np.int64).repeat(nobj)  # (panel, frame)-major, the objects innermost
     obj = np.tile(np.arange(nobj, dtype=np.int64), P * n)
-    dist, _, inside = ms.distance(pts.reshape(-1, 3), obj.astype(np.int32), inv[obj, slot % n], slot * V, np.full(slot.shape, V, np.int64))
+    dist, _, inside = ms.distance(pts.reshape(-1, 3), obj.astype(np.int32), inv[obj, slot % n], slot * V, np.full(slot.shape, V, np.int64),
+                                  inside=sign == "parity")
+    if sign == "winding":
+        from ..winding import WindingSet
+
+        ws = WindingSet([(item["obj_verts"][k], item["obj_faces"][k]) for k in range(nobj)], device=device)
+        _, inside = ws.points(pts.reshape(-1, 3), obj.astype(np.int32), inv[obj, slot % n], slot * V, np.full(slot.shape, V, np.int64))
     dist, inside = dist.reshape(P, n, nobj, V), inside.reshape(P, n, nobj, V)
     return torch.where(inside, dist, torch.zeros_like(dist)).amax(dim=2), inside.any(dim=2)
 
 
-def penetration_maps(item, hands, frames, far_mm, device):
+def penetration_maps(item, hands, frames, far_mm, device, sign="parity"):
     """the heat maps of a clip's hand panels: [colours (n, V, 3) float32 on the device, one per panel]"""
     from .. import render as R
 
-    depth, inside = penetration_depths(item, hands, frames, device)
+    depth, inside = penetration_depths(item, hands, frames, device, sign)
     return [R.penetration_colors(depth[p], inside[p], colour, hot=PENETRATION_COLOR, far=1e-3 * far_mm) for p, (_, colour) in enumerate(hands)]
 
 

@@ -8,7 +8,8 @@
     process_sdf(verts, faces, ...)            the reference's SDFData fields (dev_fn/util/sdf_util.py:59-99), all twelve, without pysdf
 
 The distance is unsigned and exact to the stated definition; the sign, where one is given (`inside`, process_sdf's `sdf`), is that of
-the reference's check_mesh_contains (geometry.mesh_contains / voxelize_lattice), which presumes a closed mesh - not pysdf's."""
+the reference's check_mesh_contains (geometry.mesh_contains / voxelize_lattice), which presumes a closed mesh - not pysdf's.
+process_sdf(sign="winding") takes the sign from the generalized winding number instead (winding.py), for meshes that are not closed."""
 from __future__ import annotations
 
 from ctypes import c_char_p, c_int32, c_int64, c_uint32, c_void_p
@@ -292,23 +293,29 @@ def sdf_fields(verts, ax: Dict, dist: np.ndarray, mask: np.ndarray, bbox_expand_
     return fields, {"n_inside": int(mask.sum()), "n_surface_points": int((mask & (dist == 0)).sum())}
 
 
-def process_sdf(verts, faces, bbox_expand_ratio: float = 1.2, resolution: int = 100, device=None, cull: bool = True, info: bool = False):
+def process_sdf(verts, faces, bbox_expand_ratio: float = 1.2, resolution: int = 100, device=None, cull: bool = True, info: bool = False,
+                sign: str = "parity"):
     """The reference's process_sdf without pysdf: the dict of all twelve SDFData fields (SDF_FIELDS; `SDFData(**fields)` takes it).
     The numpy-line fields are those of metrics/siv.lattice_axes; `sdf` = +dist where geometry.voxelize_lattice says inside, -dist
     elsewhere (the reference's "negative outside"), float64; `point` = query point + mesh_center.  `sdf > 0` differs from the inside
     mask only on interior lattice points whose distance is exactly 0: with `info` the call returns (fields, {"n_inside",
-    "n_surface_points"}), where n_surface_points counts exactly those."""
+    "n_surface_points"}), where n_surface_points counts exactly those.
+    sign="winding": the mask is winding.lattice_winding's `inside` (|w| > 0.5, include/tamf_winding.h) - the sign for a mesh that is
+    open or scanned; the distance is as before."""
     import torch
 
     from .geometry import voxelize_lattice
     from .metrics.siv import lattice_axes
+    from .winding import check_sign, lattice_winding
+
+    check_sign(sign)
 
     ax = lattice_axes(verts, bbox_expand_ratio, resolution)
     f = np.asarray(faces)
     tk = torch.from_numpy(np.ascontiguousarray(ax["ticks"]))
     if device is not None:
         tk = tk.to(device)
-    mask = voxelize_lattice(ax["verts_centred"], f, tk)
+    mask = voxelize_lattice(ax["verts_centred"], f, tk) if sign == "parity" else lattice_winding(ax["verts_centred"], f, tk, device=device)[1]
     dist = lattice_distance(ax["verts_centred"], f, tk, cull=cull, device=mask.device)
     fields, extra = sdf_fields(verts, ax, dist.reshape(-1).cpu().numpy(), mask.reshape(-1).cpu().numpy(), bbox_expand_ratio, resolution)
     return (fields, extra) if info else fields

@@ -67,10 +67,16 @@ def reduce_frames(dist, inside, jobs: Dict[str, np.ndarray], n_verts: int) -> Tu
 
 
 def clip_pd(hand_verts_gt, hand_verts_refined, obj_traj, mesh_set, mesh_ids: Sequence[Optional[int]], avai_len: int, stride: int = STRIDE,
-            cull: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+            cull: bool = True, sign: str = "parity", winding_set=None) -> Tuple[np.ndarray, np.ndarray]:
     """Penetration depth of every sampled frame of one clip -> depth (2, n_frames) in cm, penetrating (2, n_frames) bool; row 0 the
     ground-truth hand, row 1 the refined one.  hand_verts_* (T, V, 3) float32, obj_traj (nobj, T, 9) = [tsl | rot6d] (float32 in the
-    dataset), mesh_set a meshdist.MeshSet, mesh_ids[o] the clip's object o in it or None (no mesh: left out)."""
+    dataset), mesh_set a meshdist.MeshSet, mesh_ids[o] the clip's object o in it or None (no mesh: left out).
+    sign="winding": `inside` comes from winding_set (a winding.WindingSet of the same meshes in the same order) on the same jobs and
+    transforms - the generalized winding number, for object meshes that are not closed; the distance is mesh_set's as before."""
+    from ..winding import check_sign
+
+    if check_sign(sign) == "winding" and winding_set is None:
+        raise ValueError("clip_pd: sign='winding' needs winding_set, a winding.WindingSet of mesh_set's meshes")
     avai_len = int(avai_len)
     gt = np.asarray(hand_verts_gt, dtype=np.float32)[:avai_len]
     rf = np.asarray(hand_verts_refined, dtype=np.float32)[:avai_len]
@@ -83,7 +89,9 @@ def clip_pd(hand_verts_gt, hand_verts_refined, obj_traj, mesh_set, mesh_ids: Seq
     hands = np.ascontiguousarray(np.stack([gt[frames], rf[frames]], axis=1).reshape(2 * n * V, 3))
     inv = inverse_transf(tslrot6d_to_transf(np.asarray(obj_traj)[:, :avai_len]))  # (nobj, len, 3, 4), the dataset's dtype
     tr = inv[jobs["obj"], frames[jobs["frame_slot"]]].astype(np.float64)  # upcast: exact
-    dist, _, inside = mesh_set.distance(hands, jobs["mesh_id"], tr, jobs["pt_off"], jobs["pt_len"], inside=True, cull=cull)
+    dist, _, inside = mesh_set.distance(hands, jobs["mesh_id"], tr, jobs["pt_off"], jobs["pt_len"], inside=sign == "parity", cull=cull)
+    if sign == "winding":
+        _, inside = winding_set.points(hands, jobs["mesh_id"], tr, jobs["pt_off"], jobs["pt_len"], inside=True)
     return reduce_frames(dist.cpu().numpy(), inside.cpu().numpy(), jobs, V)
 
 

@@ -67,17 +67,25 @@ def lattice_points(ticks: np.ndarray, mesh_center: np.ndarray, flat_index: np.nd
     return (q + mesh_center) + mesh_center
 
 
-def object_lattice(verts, faces, bbox_expand_ratio: float = 1.2, resolution: int = 100, device=None) -> ObjectLattice:
-    """process_sdf with the reference's check_mesh_contains as the sign (module docstring).  verts (V,3), faces (F,3) of a closed mesh."""
+def object_lattice(verts, faces, bbox_expand_ratio: float = 1.2, resolution: int = 100, device=None, sign: str = "parity") -> ObjectLattice:
+    """process_sdf with the reference's check_mesh_contains as the sign (module docstring).  verts (V,3), faces (F,3) of a closed mesh.
+    sign="winding": the voxel set is that of the generalized winding number (winding.lattice_winding, |w| > 0.5), which needs no
+    closed mesh and equals the default on a clean closed one."""
     import torch
 
     from ..geometry import voxelize_lattice
+    from ..winding import check_sign, lattice_winding
+
+    check_sign(sign)
 
     ax = lattice_axes(verts, bbox_expand_ratio, resolution)
     tk = torch.from_numpy(np.ascontiguousarray(ax["ticks"]))
     if device is not None:
         tk = tk.to(device)
-    mask = voxelize_lattice(ax["verts_centred"], np.asarray(faces), tk)
+    if sign == "parity":
+        mask = voxelize_lattice(ax["verts_centred"], np.asarray(faces), tk)
+    else:
+        mask = lattice_winding(ax["verts_centred"], np.asarray(faces), tk, device=device)[1]
     idx = torch.nonzero(mask.reshape(-1)).reshape(-1).cpu().numpy()  # ascending
     return ObjectLattice(mesh_center=ax["mesh_center"], extent=ax["extent"], extent_expanded=ax["extent_expanded"], tick_unit=ax["tick_unit"],
                          ticks=ax["ticks"], points_in=lattice_points(ax["ticks"], ax["mesh_center"], idx),
